@@ -17,15 +17,24 @@ A line is only ever printed with n_gpus == --gpus; every line carries `fallback_
 time-outs, contexts that left the one-XCD hand-off form, sets recomputed on the regular route, summed over the ranks).
 
 Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` for the dominant
-kernel (the Gram MFMA kernel, timed with HIP events on its own stream inside the timed region)
-and `cpu_baseline` (the NumPy/SciPy oracle -- the reference's exact library calls -- on a bounded
-row sample, rank 0, N = 1 only).
+kernel (the Gram MFMA kernel, timed with HIP events on its own stream inside the timed region).
+A plain run does only that: set up, warm up, time the K steps, write the outputs (--dump-outputs DIR) and print.
 
-The metric has a second half, "reduced timesteps/s" (BASELINE.json configs[4]: 1e4 timesteps x 32 parameter
-points, r = 80; single GPU by the north star).  At N = 1 the same process therefore also runs, after the POD
-region, the online sweep of that configuration twice - the direct path (V^T(A V) on the matrix cores every step,
-N_h = 1e5) and the hyper-reduced path ((M)DEIM expansions, nothing of size N_h) - and reports both under
-`secondary`, each with its own `roofline` / `cpu_baseline` (--no-secondary skips it).
+--full adds, after the timed region, everything the headline does not need:
+  * at N = 1 the single-POD latency runs (`config.single_pod_latency_ms`) and the Gram launched on the whole chip
+    (`roofline.whole_chip_launch`) - --no-latency skips them;
+  * `cpu_baseline` (the NumPy/SciPy oracle -- the reference's exact library calls -- on a bounded row sample,
+    rank 0, N = 1 only) - --no-cpu-baseline skips it;
+  * the metric's second half, "reduced timesteps/s" (BASELINE.json configs[4]: 1e4 timesteps x 32 parameter
+    points, r = 80; single GPU by the north star): at N = 1 the online sweep of that configuration twice - the
+    direct path (V^T(A V) on the matrix cores every step, N_h = 1e5) and the hyper-reduced path ((M)DEIM
+    expansions, nothing of size N_h) - reported under `secondary`, each with its own `roofline` / `cpu_baseline`
+    (--no-secondary skips it).
+
+--dump-outputs DIR writes what the last timed step returned, as a caller of orth() receives it: `s.npy` and
+`energy.npy` (all n values) and `Q_sample.npy`, the rows of the basis Q at DUMP_ROWS row indices drawn once from
+a generator seeded with SEED (sorted; the same for every run with the same --rows), all float64.  The snapshot
+matrix depends on the arguments only (seeded generators), so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -43,6 +52,8 @@ CHUNK_ROWS = 125_000          # the global matrix is generated in 8 fixed chunks
 SEED = 20260104 + 3
 FP64_MFMA_PEAK_TFLOPS = 78.6  # MI355X FP64 matrix peak (AMD spec) -- the guide lists no f64 row
 HBM_PEAK_GBS = 8000.0         # MI355X_MICROARCH.md: HBM3E 8 TB/s
+DUMP_ROWS = 65_536            # rows of Q written by --dump-outputs (at r = 40: 21 MB)
+DUMP_BYTES_MAX = 48 << 20     # cap on the Q sample, whatever --modes is
 
 
 def spectrum(n):
@@ -73,6 +84,36 @@ def build_local_matrix(rank, world, n_h, n, device):
         parts.append(make_chunk(c, rows, n, mix, device))
     X = torch.cat(parts, dim=0) if len(parts) > 1 else parts[0]
     return X.contiguous()
+
+
+def local_row_offset(rank, world, n_h):
+    """First global row of this rank's slab (build_local_matrix's chunk arithmetic)."""
+    n_chunks = (n_h + CHUNK_ROWS - 1) // CHUNK_ROWS
+    per_rank = (n_chunks + world - 1) // world
+    return min(n_h, rank * per_rank * CHUNK_ROWS)
+
+
+def dump_outputs(path, result, n_h, rank, world, device, distributed):
+    """--dump-outputs: the last timed step's Q (a fixed, seeded row sample), s and energy as float64 .npy files.
+    Q is row-sharded over the ranks: each rank fills the sampled rows it holds and the sample is summed on rank 0."""
+    Q = result["Q"]
+    r = Q.shape[1]
+    m = max(1, min(n_h, DUMP_ROWS, DUMP_BYTES_MAX // (8 * max(r, 1))))
+    rows = np.sort(np.random.default_rng(SEED).choice(n_h, size=m, replace=False))
+    lo = local_row_offset(rank, world, n_h)
+    mine = np.nonzero((rows >= lo) & (rows < lo + Q.shape[0]))[0]
+    sample = torch.zeros((m, r), dtype=torch.float64, device=device)
+    if mine.size:
+        sample[torch.from_numpy(mine).to(device)] = Q[torch.from_numpy(rows[mine] - lo).to(device)].to(torch.float64)
+    if distributed:
+        import torch.distributed as dist
+
+        dist.all_reduce(sample, op=dist.ReduceOp.SUM)
+    if rank == 0:
+        os.makedirs(path, exist_ok=True)
+        np.save(os.path.join(path, "Q_sample.npy"), sample.cpu().numpy())
+        np.save(os.path.join(path, "s.npy"), np.asarray(result["s"], dtype=np.float64))
+        np.save(os.path.join(path, "energy.npy"), np.asarray(result["energy"], dtype=np.float64))
 
 
 def cpu_baseline(X_host, r, device_result=None):
@@ -327,19 +368,27 @@ def main():
     ap.add_argument("--cols", type=int, default=N_S)
     ap.add_argument("--modes", type=int, default=R_MODES)
     ap.add_argument("--cpu-sample-rows", type=int, default=1_000_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the online-sweep half of the metric (N = 1 only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="with --full: skip the online-sweep half of the metric (N = 1 only)")
     ap.add_argument("--sweep-steps", type=int, default=10_000)
     ap.add_argument("--no-latency", action="store_true",
-                    help="pipeline mode: skip the 8 single-POD (latency mode) runs after the timed region - used under "
-                         "rocprofv3 so that the kernel statistics are those of the timed region's kernels only")
+                    help="with --full, pipeline mode: skip the 8 single-POD (latency mode) runs after the timed region - "
+                         "used under rocprofv3 so that the kernel statistics are those of the timed region's kernels only")
     ap.add_argument("--mode", choices=("auto", "pipeline", "latency"), default="auto",
                     help="pipeline: the steps run through PodPipeline (eigensolve of step i beside the Gram of step i+1 on "
                          "CU-partitioned streams); latency: one pod_device call after the other; auto = pipeline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the single-POD latency runs and the whole-chip Gram, the CPU "
+                         "baseline and the online-sweep half of the metric (N = 1); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (Q_sample.npy, s.npy, energy.npy; float64) into DIR")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves.  This process has not touched the
         # GPU (importing torch does not) and never will: it only waits for its children.
@@ -424,19 +473,29 @@ def main():
         if float(ok.item()) == 0.0:
             pipe, mode = None, f"latency (pipeline unavailable: {why_not})"
     if pipe is not None:
-        pipe.map([X] * max(args.warmup, 1), num=r, normalize=True)
+        # Results are handed out one at a time and dropped when the next arrives, as walks.pod_sequence consumes the
+        # pipeline: memory stays at a few sets in flight whatever the step count, and the allocator's blocks are reused
+        # from step to step (collecting all K bases, 320 MB each, made every timed step allocate fresh device memory).
+        def sequence(k):
+            res = None
+            for res in pipe.run([X] * k, num=r, normalize=True):
+                pass
+            return res
+
+        sequence(max(args.warmup, 1))
         pipe.gram_kernel_ms.clear()
         barrier()
         t0 = time.perf_counter()
-        outs = pipe.map([X] * args.steps, num=r, normalize=True)
+        last = sequence(args.steps)
         barrier()
         elapsed = time.perf_counter() - t0
-        out = dict(passes=outs[-1]["passes"])
-        kept = dict(Q=outs[-1]["Q"], s=outs[-1]["s"], energy=outs[-1]["energy"])   # for cpu_baseline.parity
+        out = dict(passes=last["passes"])
+        kept = dict(Q=last["Q"], s=last["s"], energy=last["energy"])   # for cpu_baseline.parity and --dump-outputs
+        del last
         gram_ms = list(pipe.gram_kernel_ms)
         stage_ms = dict(pipe.last_stage_ms, sets_recomputed_on_regular_route=float(pipe.recomputed),
                         eigensolver_cus=float(pipe.eig_cus))
-        if world == 1 and not args.no_latency:   # one POD on its own (latency mode), for the record
+        if world == 1 and args.full and not args.no_latency:   # one POD on its own (latency mode), for the record
             for _ in range(3):
                 pod.pod_device(X, num=r, normalize=True)
             torch.cuda.synchronize()
@@ -458,7 +517,6 @@ def main():
                 whole.append(ctx.last_gram_ms())
             ctx.set_profile(False)
             whole_chip_gram_ms = float(np.mean(whole))
-        del outs
         pipe.close()
         counts = [pipe.ctxE.counter(c) + ctx.counter(c) for c in FALLBACK_COUNTERS[:3]] + [pipe.recomputed]
         del pipe
@@ -499,6 +557,8 @@ def main():
         dist.all_reduce(fb, op=dist.ReduceOp.SUM)
     elapsed = float(t.item())
     fallback = {name: int(v) for name, v in zip(FALLBACK_COUNTERS, fb.tolist())}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, kept, n_h, rank, world, device, distributed)
 
     if rank == 0:
         pipe_mode = mode == "pipeline"
@@ -543,12 +603,12 @@ def main():
         line["stage_ms"] = {k: round(v, 4) for k, v in stage_ms.items()}
         line["roofline"] = roofline
         line["fallback_counters"] = fallback
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             rows = min(args.cpu_sample_rows, n_h)
             X_host = X[:rows].cpu().numpy()          # the workload's own matrix (device and host RNG streams differ)
             line["cpu_baseline"] = cpu_baseline(X_host, r, device_result=kept if rows == n_h else None)
             del X_host
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             del X, out
             torch.cuda.empty_cache()
             line["secondary"] = secondary_online_sweep(ctx, device, nt=args.sweep_steps, n_mu=32, r=80, n_h=100_000,

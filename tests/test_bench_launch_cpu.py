@@ -62,3 +62,13 @@ def test_no_gpu_for_the_ranks_is_an_error_not_a_one_rank_line():
     res = run(["--gpus", "2"])
     assert res.returncode != 0
     assert not json_lines(res.stdout)
+
+
+def test_full_and_dump_outputs_are_options_and_steps_must_be_positive(tmp_path):
+    res = run(["--gpus", "1", "--steps", "2", "--warmup", "0", "--full", "--dump-outputs", str(tmp_path / "out")],
+              ROMTIME_BENCH_DRYRUN="1")
+    assert res.returncode == 0, res.stderr[-2000:]
+    (line,) = json_lines(res.stdout)
+    assert line["steps"] == 2 and line["warmup"] == 0
+    res = run(["--gpus", "1", "--steps", "0"], ROMTIME_BENCH_DRYRUN="1")
+    assert res.returncode != 0 and not json_lines(res.stdout)

@@ -5,11 +5,9 @@ ROM pair of ``RomConstructorNonlinear`` with all six operators hyper-reduced, va
 by ``compute_rom_difference``.  The fixture tests/golden/hrom.npz holds what the reference's driver + the reference's
 classes produce on the closed-form Burgers mock (tests/golden/make_golden.py::gen_hrom).
 
-Two checks:
-  * ``PistonWorkflow`` below replays the driver's call sequence on romtime_amd's classes - runs anywhere, on the CPU
-    stub and on the HIP path (-m gpu; the reference is not on the GPU box);
-  * where /root/reference exists (the build container), the REFERENCE'S OWN DRIVER CODE is run with the class names it
-    imported re-pointed to romtime_amd's classes - the drop-in claim itself (host logic on the CPU stub).
+``PistonWorkflow`` below replays the driver's call sequence on romtime_amd's classes - on the CPU stub and on the HIP
+path (-m gpu).  (tests/golden/make_golden.py::run_piston_driver also runs the driver's own code over these classes where
+the reference's source is at hand; that source is not part of this repository, so the suite checks the recorded run.)
 Bars: kept-mode counts, interpolation entries, sampled online parameters identical; FOM-space trajectories within 2e-6
 rel-L2 (the reference's GMRES stops at 1e-10, rom.py:36 - SURVEY hard part E); error / estimator curves rtol 1e-4."""
 import os
@@ -263,36 +261,3 @@ def test_piston_workflow_hostlogic(cpu_ops, golden_hrom, tmp_path, monkeypatch):
 @pytest.mark.gpu
 def test_piston_workflow_hip(golden_hrom, tmp_path, monkeypatch):
     check_piston_workflow(golden_hrom, tmp_path, monkeypatch)
-
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="needs the reference tree (build container only)")
-def test_reference_driver_over_romtime_amd_classes(cpu_ops, golden_hrom):
-    """The drop-in claim: rom/hrom.py's OWN code (HyperReducedPiston.run_offline_rom, run_offline_hyperreduction,
-    project_reductors, evaluate_validation, evaluate_online) with ``RomConstructorNonlinear``, the three (M)DEIM
-    classes and ``compute_rom_difference`` re-pointed to romtime_amd's reproduces the run it makes on its own classes."""
-    import romtime_amd
-    from romtime_amd import utils
-    from romtime_amd.base import Reductor
-    from tests.golden import make_golden as mg
-
-    ref = mg.load_reference()
-    classes = dict(rom=romtime_amd.RomConstructorNonlinear, deim=romtime_amd.DiscreteEmpiricalInterpolation,
-                   mdeim=romtime_amd.MatrixDiscreteEmpiricalInterpolation,
-                   nmdeim=romtime_amd.MatrixDiscreteEmpiricalInterpolationNonlinear, reductor=Reductor,
-                   compute_rom_difference=utils.compute_rom_difference)
-    data, H = mg.run_piston_driver(ref, classes)
-    assert type(H.rom).__module__.startswith("romtime_amd") and type(H.mdeim_trilinear).__module__.startswith("romtime_amd")
-    g = golden_hrom
-    for key in ("N_rom", "N_srom", "N__rhs", "N__mass", "N__stiffness", "N__convection", "N__nonlinear_lifting",
-                "N__trilinear"):
-        assert int(data[key]) == int(g[key]), key
-    assert_allclose(data["online_mus"], g["online_mus"], rtol=1e-14)
-    assert list(data["files_written"]) == list(g["files_written"])              # same artefacts, same names
-    for key in g.files:
-        if key.startswith("dofs__") and not bool(g["cluster__" + key[6:]]):
-            np.testing.assert_array_equal(data[key], g[key], err_msg=key)
-        elif key.startswith(("rom_uh__", "srom_uh__")):
-            assert np.linalg.norm(data[key] - g[key]) <= 2e-6 * np.linalg.norm(g[key]), key
-        elif key.startswith(("errors__", "resume_errors__")):   # resume_*: start_from_existing_basis (hrom.py:344-417)
-            assert_allclose(data[key], g[key], rtol=1e-4, atol=1e-6 * g[key].max(), err_msg=key)
-    assert (int(data["resume_N_rom"]), int(data["resume_N_srom"])) == (int(g["resume_N_rom"]), int(g["resume_N_srom"]))

@@ -11,7 +11,7 @@ mkdir -p $O $DEST
 export PYTHONPATH=$R
 cd /tmp && export TMPDIR=/tmp
 B="python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --no-latency"
-python3 $R/bench.py > $O/bench.log 2>&1 || exit 1
+python3 $R/bench.py --full > $O/bench.log 2>&1 || exit 1
 tail -1 $O/bench.log > $DEST/${ROUND}_bench_${TAG}.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --no-cpu-baseline --no-secondary --no-latency > $O/stats.log 2>&1 || exit 2
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -- $B > $O/fetch.log 2>&1 || exit 3
