@@ -116,6 +116,7 @@ extern "C" int rt_rank_update(rt_ctx* ctx, const double* Ysrc, int64_t ldys, con
   if (gx > stages) gx = stages;
   hipLaunchKernelGGL(rank_update_kernel, dim3((unsigned)gx, gy), dim3(RU_THREADS), lds, ctx->stream, p);
   RT_HIP_CHECK(ctx, hipGetLastError());
+  ctx->last_grid = gx * gy; ctx->last_splits = 1; ctx->last_tile = RU_ROWS * 1000 + RU_COLS;
   return RT_OK;
 }
 

@@ -132,6 +132,7 @@ int rt_expansion_gemm(rt_ctx* ctx, const double* G, long ldg, const double* Z, l
   }
 #undef EX_LAUNCH
   RT_HIP_CHECK(ctx, hipGetLastError());
+  ctx->last_grid = grid.x; ctx->last_splits = 1; ctx->last_tile = 64 * 1000 + 32;
   return RT_OK;
 }
 
