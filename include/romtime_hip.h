@@ -59,7 +59,8 @@ int rt_ctx_set_profile(rt_ctx* ctx, int on);
  * two eigensolves in flight on the SAME XCD would starve each other of CUs (they end in the hand-off's time-out).
  * "sweep_graph" (default 0): rt_hrom_bdf_sweep captures one time step as a hipGraph (its kernels read the step from a
  * device counter) and replays it for steps 1 .. nt-1 instead of launching two kernels per step; for hosts that
- * cannot keep ahead of the device.  The call then returns only when the sweep has finished. */
+ * cannot keep ahead of the device.  The call then returns only when the sweep has finished.  Ignored while the ctx's
+ * reduced solver is RT_SOLVER_GMRES (rt_ctx_set_reduced_solver): the launches are then eager. */
 int rt_ctx_set_option(rt_ctx* ctx, const char* name, int value);
 /* "cu_limit" (default 0 = the device's CU count; a multiple of 8): the number of CUs this ctx sizes its persistent grids
  * for - set it on a ctx whose stream is CU-masked (below) so that, e.g., the snapshot Gram kernel launches exactly the
@@ -80,7 +81,9 @@ int rt_last_gemm_ms(rt_ctx* ctx, double* ms);
  * bound: results of that call were invalid and the caller took another route), "eig_one_xcd" / "eig_general_form"
  * (tridiagonalisations that ran each hand-off form), "gram_off_xcd" (workgroups of the snapshot Gram kernel that ran on
  * another XCD than the one their K range was laid out for: should stay 0), "sweep_newton_iterations", "sweep_restarts",
- * "sweep_lu_fallbacks", "sweep_solves" (the four numbers of rt_last_sweep_stats). */
+ * "sweep_lu_fallbacks", "sweep_solves" (the four numbers of rt_last_sweep_stats), "sweep_gmres_iterations" (GMRES inner
+ * iterations of the most recent sweep, RT_SOLVER_GMRES), "sweep_gmres_unconverged" (its systems that GMRES left with
+ * info != 0).  All six sweep counters are zeroed at the start of every sweep, whatever its solver. */
 int rt_ctx_get_counter(rt_ctx* ctx, const char* name, int64_t* value);
 /* The same for the most recent launch of the snapshot Gram kernel (rt_gram, n >= 97, long X): its own event pair,
  * so it can be read at the end of a POD step, after the GEMMs that followed it, without holding the host back. */
@@ -219,6 +222,29 @@ int rt_dense_solve_multi(rt_ctx* ctx, const double* K, int64_t r, const double* 
 int rt_tracked_solve_batched(rt_ctx* ctx, const double* K, double* Xinv, double* rhs, int64_t r, int64_t B, int have_prev,
                              int* info);
 
+/* ---- GMRES reduced solve: the reference's own solver, scipy.sparse.linalg.gmres(K_N, b_N, atol=1e-10, tol=1e-10,
+ *      maxiter=1e6) with restart 20, x0 = 0, no preconditioner and info never checked (rom.py:36,414-425,492) ---------- */
+#define RT_SOLVER_DIRECT 0   /* default: tracked inverse / pivoted LU, as above */
+#define RT_SOLVER_GMRES 1    /* restarted GMRES with SciPy's stopping decisions */
+typedef struct {
+  double rtol, atol;         /* SciPy's rtol (rom.py:36 spells it tol) and atol; >= 0 */
+  int64_t restart, maxiter;  /* Krylov dimension of a cycle (min(restart, r) is used) and outer cycles; >= 1 */
+} rt_gmres_opts;             /* host struct */
+/* x_b with K_b x_b = b_b for b < B: the control flow of SciPy 1.15's gmres step for step (norms, modified Gram-Schmidt,
+ * breakdown test h1 <= eps h0, Givens rotations with LAPACK dlartg semantics, the inner test presid <= ptol, SciPy's
+ * back substitution, the outer test and the ptol update), so the stopping decisions and the iterate are SciPy's up to
+ * rounding.  K (B x r x r row-major), b and x (B x r) are DEVICE arrays; r <= 128 (RT_ERR_UNSUPPORTED beyond), options
+ * out of range RT_ERR_ARG.  info (B device int64, may be NULL): SciPy's info, 0 or maxiter (|b - K x| > max(atol,
+ * rtol |b|)); iters (B device ints, may be NULL): inner iterations, i.e. the calls of a callback_type="pr_norm" callback.
+ * One wave per system; a system's result does not depend on B or on its place in the batch. */
+int rt_gmres_batched(rt_ctx* ctx, const double* K, const double* b, double* x, int64_t r, int64_t B,
+                     const rt_gmres_opts* opts, int64_t* info, int* iters);
+/* What rt_rom_bdf_sweep / rt_hrom_bdf_sweep solve each step's systems with: RT_SOLVER_DIRECT (the default; opts may be
+ * NULL) or RT_SOLVER_GMRES with opts (copied).  In GMRES mode a step's systems go to one GMRES launch that also forms
+ * b_N and closes the step; "sweep_graph" is ignored; "sweep_solves", "sweep_gmres_iterations" and
+ * "sweep_gmres_unconverged" tell what happened. */
+int rt_ctx_set_reduced_solver(rt_ctx* ctx, int kind, const rt_gmres_opts* opts);
+
 /* ---- online sweep (RomConstructor*.solve, rom/rom.py:430-555, :877-929) on the device --------- */
 typedef struct {
   int64_t N, nnz, r, n_mu, nt;   /* DoFs, pattern nonzeros, reduced size (<= 128), parameter points, time steps */
@@ -267,7 +293,7 @@ typedef struct {
  * No quantity of size N_h is touched.  uN_out: n_mu x nt x r (device). */
 int rt_hrom_bdf_sweep(rt_ctx* ctx, const rt_hsweep_desc* desc, double* uN_out);
 /* How the reduced systems of the most recent sweep on this ctx were solved (the reference calls GMRES once per step,
- * rom.py:492; here K_N^-1 is tracked from step to step): stats4 = { Newton-Schulz iterations, systems restarted from
+ * rom.py:492; by default K_N^-1 is tracked from step to step): stats4 = { Newton-Schulz iterations, systems restarted from
  * K^T/(|K|_1 |K|_inf), systems handed to the pivoted LU, systems solved }.  Synchronises the ctx stream. */
 int rt_last_sweep_stats(rt_ctx* ctx, int64_t* stats4);
 

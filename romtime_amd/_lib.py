@@ -22,6 +22,15 @@ _p = C.c_void_p
 _i64 = C.c_int64
 _int = C.c_int
 
+SOLVER_DIRECT, SOLVER_GMRES = 0, 1
+
+
+class GmresOpts(C.Structure):
+    """rt_gmres_opts of include/romtime_hip.h (built from SciPy-style options by romtime_amd.gmres.gmres_opts)."""
+
+    _fields_ = [("rtol", C.c_double), ("atol", C.c_double), ("restart", _i64), ("maxiter", _i64)]
+
+
 # name -> (restype, argtypes); mirrors include/romtime_hip.h one to one
 SIGNATURES = {
     "rt_version": (_int, []),
@@ -58,6 +67,8 @@ SIGNATURES = {
     "rt_dense_solve_batched": (_int, [_p, _p, _p, _i64, _i64, _p]),
     "rt_dense_solve_multi": (_int, [_p, _p, _i64, _p, _p, _i64, _p]),
     "rt_tracked_solve_batched": (_int, [_p, _p, _p, _p, _i64, _i64, _int, _p]),
+    "rt_gmres_batched": (_int, [_p, _p, _p, _p, _i64, _i64, C.POINTER(GmresOpts), _p, _p]),
+    "rt_ctx_set_reduced_solver": (_int, [_p, _int, C.POINTER(GmresOpts)]),
     "rt_rom_bdf_sweep": (_int, [_p, _p, _p]),
     "rt_hrom_bdf_sweep": (_int, [_p, _p, _p]),
     "rt_p1_local_assembly": (_int, [_p, _int, _i64, _p, _p, _i64, _i64, _p, _p, _int, _p, _p]),
@@ -136,6 +147,7 @@ class Context:
             raise RomtimeHipError(f"rt_ctx_create(device={device}) failed with {rc}")
         self.handle = h
         self.options = {}
+        self.reduced_solver = (SOLVER_DIRECT, None)   # (kind, GmresOpts or None), as last set on the ctx
         self._pid = os.getpid()
         with Context._live_lock:
             Context._live.add(self)
@@ -228,6 +240,13 @@ class Context:
     def set_option(self, name: str, value: int):
         self.check(self.lib.rt_ctx_set_option(self.handle, name.encode(), int(value)), "rt_ctx_set_option")
         self.options[name] = int(value)
+
+    def set_reduced_solver(self, kind: int, opts: GmresOpts = None):
+        """What the online sweeps solve their reduced systems with (rt_ctx_set_reduced_solver): SOLVER_DIRECT, or
+        SOLVER_GMRES with ``opts``."""
+        self.check(self.lib.rt_ctx_set_reduced_solver(self.handle, int(kind), C.byref(opts) if opts is not None else None),
+                   "rt_ctx_set_reduced_solver")
+        self.reduced_solver = (int(kind), opts)
 
     def set_profile(self, on: bool):
         self.profiling = bool(on)

@@ -165,7 +165,7 @@ int rt_func_lds(rt_ctx* ctx, const void* fn, int bytes) {
 
 extern "C" {
 
-int rt_version(void) { return 320; }  // 320: rt_gram_plan_info; 310: option gram_pace (paced / one-launch Gram); 300 (round 3): rt_dense_solve_multi, RT_P1_LOAD_P2; 210: rt_tracked_solve_batched, rt_pod_enqueue, options eig_xcd, counter gram_off_xcd
+int rt_version(void) { return 330; }  // 330: rt_gmres_batched, rt_ctx_set_reduced_solver, counters sweep_gmres_*; 320: rt_gram_plan_info; 310: option gram_pace (paced / one-launch Gram); 300 (round 3): rt_dense_solve_multi, RT_P1_LOAD_P2; 210: rt_tracked_solve_batched, rt_pod_enqueue, options eig_xcd, counter gram_off_xcd
 
 int rt_ctx_create(rt_ctx** out, int device) {
   if (!out) return RT_ERR_ARG;
@@ -296,7 +296,8 @@ int rt_ctx_get_counter(rt_ctx* ctx, const char* name, int64_t* value) {
   static const struct { const char* name; int slot; } table[] = {
       {"eig_timeouts", RT_CNT_EIG_TIMEOUT}, {"eig_general_form", RT_CNT_EIG_GENERAL_FORM},
       {"eig_one_xcd", RT_CNT_EIG_ONE_XCD}, {"gram_off_xcd", RT_CNT_GRAM_OFF_XCD}, {"sweep_newton_iterations", RT_CNT_NS_ITER},
-      {"sweep_restarts", RT_CNT_NS_RESTART}, {"sweep_lu_fallbacks", RT_CNT_LU_FALLBACK}, {"sweep_solves", RT_CNT_SOLVES}};
+      {"sweep_restarts", RT_CNT_NS_RESTART}, {"sweep_lu_fallbacks", RT_CNT_LU_FALLBACK}, {"sweep_solves", RT_CNT_SOLVES},
+      {"sweep_gmres_iterations", RT_CNT_GMRES_ITER}, {"sweep_gmres_unconverged", RT_CNT_GMRES_UNCONVERGED}};
   for (const auto& t : table)
     if (key == t.name) {
       long host = 0;

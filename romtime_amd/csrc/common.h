@@ -7,7 +7,7 @@
 
 #include "../../include/romtime_hip.h"
 
-constexpr int RT_N_COUNTERS = 8;
+constexpr int RT_N_COUNTERS = 10;
 
 struct rt_ctx {
   int device = 0;
@@ -44,6 +44,8 @@ struct rt_ctx {
   // started}, 128 B apart); zeroed when allocated and again by every Gram's reduction kernel
   unsigned long long* gram_pace = nullptr;
   bool gram_pace_on = true;         // "gram_pace" option
+  int reduced_solver = RT_SOLVER_DIRECT;      // what the two sweeps solve their systems with (rt_ctx_set_reduced_solver)
+  rt_gmres_opts gmres_opts{1e-5, 0.0, 20, 1}; // ... and the options of RT_SOLVER_GMRES
 };
 
 // slots of rt_ctx::dev_counters
@@ -55,7 +57,9 @@ enum {
   RT_CNT_NS_ITER = 4,           // online sweep: Newton-Schulz iterations (zeroed at the start of every sweep)
   RT_CNT_NS_RESTART = 5,        // ... systems restarted from K^T / (|K|_1 |K|_inf)
   RT_CNT_LU_FALLBACK = 6,       // ... systems handed to the pivoted LU
-  RT_CNT_SOLVES = 7             // ... systems solved
+  RT_CNT_SOLVES = 7,            // ... systems solved
+  RT_CNT_GMRES_ITER = 8,        // ... GMRES inner iterations (RT_SOLVER_GMRES)
+  RT_CNT_GMRES_UNCONVERGED = 9  // ... systems GMRES left with info != 0
 };
 
 #define RT_TRY(expr)                 \
@@ -132,6 +136,15 @@ struct rt_advance;  // sweep_advance.h: the hyper-reduced sweep's end-of-step wo
 int rt_newton_solve_batched(rt_ctx* ctx, const double* K, double* Xinv, double* rhs, int64_t r, int64_t B,
                             int have_prev, int* info, const rt_newton_rhs* recipe = nullptr,
                             const rt_advance* advance = nullptr);
+
+// Restarted GMRES with SciPy's control flow (gmres.hip).  `work`: rt_gmres_work_bytes(r, B, o) bytes of device memory for
+// Krylov bases that do not fit the LDS (0 bytes when they do; nullptr: the ctx's leaf arena); recipe / advance as for
+// rt_newton_solve_batched; `count`: add to the sweep counters.
+int rt_gmres_check_opts(rt_ctx* ctx, const rt_gmres_opts* o);
+size_t rt_gmres_work_bytes(int64_t r, int64_t B, const rt_gmres_opts* o);
+int rt_gmres_launch(rt_ctx* ctx, const double* K, const double* b, double* x, int64_t r, int64_t B, const rt_gmres_opts* o,
+                    int64_t* info, int* iters, double* work, const rt_newton_rhs* recipe, const rt_advance* advance,
+                    bool count);
 
 // Fused SpMM + V^T(.) projection (project_fused.hip); RT_ERR_UNSUPPORTED for r > 128.  `stage_table` is the
 // per-pattern table built by rt_project_stage_table (rt_project_stage_table_bytes(N) bytes of device memory), or

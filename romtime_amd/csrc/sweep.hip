@@ -262,6 +262,7 @@ extern "C" int rt_rom_bdf_sweep(rt_ctx* ctx, const rt_sweep_desc* d, double* uN_
   const long N = d->N, nnz = d->nnz, r = d->r, B = d->n_mu, nt = d->nt;
   const int Q = (int)d->n_terms, F = (int)d->n_rhs;
   hipStream_t st = ctx->stream;
+  const bool gmres = ctx->reduced_solver == RT_SOLVER_GMRES;
 
   // workspace (composite arena)
   size_t off = 0;
@@ -271,7 +272,8 @@ extern "C" int rt_rom_bdf_sweep(rt_ctx* ctx, const rt_sweep_desc* d, double* uN_
                oUm = take(sizeof(double) * B * r), oUh = take(sizeof(double) * B * N), oUp = take(sizeof(double) * B * N),
                oXT = take(sizeof(double) * r * B), oInfo = take(sizeof(int) * B),
                oKv = take(sizeof(double) * B * nnz), oTab = take(rt_project_stage_table_bytes(N)),
-               oXi = take(sizeof(double) * B * r * r);
+               oXi = take(sizeof(double) * B * r * r),
+               oGw = take(gmres ? rt_gmres_work_bytes(r, B, &ctx->gmres_opts) : 0);
   void* base = nullptr;
   int rc = rt_scratch2(ctx, off, &base);
   if (rc != RT_OK) return rc;
@@ -290,10 +292,11 @@ extern "C" int rt_rom_bdf_sweep(rt_ctx* ctx, const rt_sweep_desc* d, double* uN_
   double* kval = reinterpret_cast<double*>(b8 + oKv);
   double* Xinv = reinterpret_cast<double*>(b8 + oXi);  // K_N^-1 of the previous step, per parameter point
   void* stage_table = b8 + oTab;  // per-pattern stage records of the fused projection, built once per sweep
+  double* gwork = reinterpret_cast<double*>(b8 + oGw);  // GMRES mode: Krylov bases that do not fit the LDS
 
   RT_HIP_CHECK(ctx, hipMemsetAsync(un, 0, sizeof(double) * B * r, st));
   RT_HIP_CHECK(ctx, hipMemsetAsync(unm1, 0, sizeof(double) * B * r, st));
-  RT_HIP_CHECK(ctx, hipMemsetAsync(ctx->dev_counters + RT_CNT_NS_ITER, 0, sizeof(long) * 4, st));  // rt_last_sweep_stats
+  RT_HIP_CHECK(ctx, hipMemsetAsync(ctx->dev_counters + RT_CNT_NS_ITER, 0, sizeof(long) * 6, st));  // stats + GMRES counters
   RT_HIP_CHECK(ctx, hipMemsetAsync(uh, 0, sizeof(double) * B * N, st));
   RT_HIP_CHECK(ctx, hipMemsetAsync(uhp, 0, sizeof(double) * B * N, st));
   hipLaunchKernelGGL(sweep_rows_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st,
@@ -336,7 +339,8 @@ extern "C" int rt_rom_bdf_sweep(rt_ctx* ctx, const rt_sweep_desc* d, double* uN_
     rt_advance close{};
     close.un = un; close.unm1 = unm1; close.out = uN_out; close.step_done = step; close.nt = nt;
     close.keep_prev = d->bdf2 ? 1 : 0; close.do_coef = 0; close.xT = xT; close.B = (int)B; close.enabled = 1;
-    rc = rt_newton_solve_batched(ctx, KN, Xinv, rhs, r, B, step > 0 ? 1 : 0, info, &rq, &close);
+    rc = gmres ? rt_gmres_launch(ctx, KN, nullptr, rhs, r, B, &ctx->gmres_opts, nullptr, nullptr, gwork, &rq, &close, true)
+               : rt_newton_solve_batched(ctx, KN, Xinv, rhs, r, B, step > 0 ? 1 : 0, info, &rq, &close);
     if (rc == RT_ERR_UNSUPPORTED) {  // r > 80: the LDS-resident iteration does not fit
       hipLaunchKernelGGL(sweep_rhs_kernel, dim3((unsigned)B), dim3(128), sizeof(double) * r, st, MN, un, unm1, c0, c1,
                          d->dt, F ? d->rhs_coef + step * B * F : nullptr, fN, F, (int)r, rhs);
@@ -372,11 +376,13 @@ extern "C" int rt_hrom_bdf_sweep(rt_ctx* ctx, const rt_hsweep_desc* d, double* u
   const long r = d->r, B = d->n_mu, nt = d->nt, mm = d->m_mass, ml = d->m_lin, mn = d->m_nl, mf = d->m_rhs;
   const long M = mm + ml + mn, rr = r * r;
   hipStream_t st = ctx->stream;
+  const bool gmres = ctx->reduced_solver == RT_SOLVER_GMRES;
   size_t off = 0;
   auto take = [&off](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
   const size_t oG = take(sizeof(double) * 2 * B * M), oKN = take(sizeof(double) * 2 * B * rr),
                oRhs = take(sizeof(double) * B * r), oUn = take(sizeof(double) * B * r), oUm = take(sizeof(double) * B * r),
-               oXi = take(sizeof(double) * B * rr), oInfo = take(sizeof(int) * B), oCtr = take(sizeof(long));
+               oXi = take(sizeof(double) * B * rr), oInfo = take(sizeof(int) * B), oCtr = take(sizeof(long)),
+               oGw = take(gmres ? rt_gmres_work_bytes(r, B, &ctx->gmres_opts) : 0);
   void* base = nullptr;
   int rc = rt_scratch2(ctx, off, &base);
   if (rc != RT_OK) return rc;
@@ -390,9 +396,10 @@ extern "C" int rt_hrom_bdf_sweep(rt_ctx* ctx, const rt_hsweep_desc* d, double* u
   double* Xinv = reinterpret_cast<double*>(b8 + oXi);
   int* info = reinterpret_cast<int*>(b8 + oInfo);
   long* ctr = reinterpret_cast<long*>(b8 + oCtr);
+  double* gwork = reinterpret_cast<double*>(b8 + oGw);
   RT_HIP_CHECK(ctx, hipMemsetAsync(un, 0, sizeof(double) * B * r, st));
   RT_HIP_CHECK(ctx, hipMemsetAsync(unm1, 0, sizeof(double) * B * r, st));
-  RT_HIP_CHECK(ctx, hipMemsetAsync(ctx->dev_counters + RT_CNT_NS_ITER, 0, sizeof(long) * 4, st));  // rt_last_sweep_stats
+  RT_HIP_CHECK(ctx, hipMemsetAsync(ctx->dev_counters + RT_CNT_NS_ITER, 0, sizeof(long) * 6, st));  // stats + GMRES counters
 
   // the end-of-step work for closing step next-1 (if any) and preparing the rows of step `next`
   auto advance_args = [&](long next) {
@@ -419,8 +426,8 @@ extern "C" int rt_hrom_bdf_sweep(rt_ctx* ctx, const rt_hsweep_desc* d, double* u
   // kernels take the step from a device counter, and replayed; step 0 runs eagerly (first BDF step, inverse tracking
   // starts, scratch arenas get their sizes).  It is an option, not the default: on the pool's boxes plain launches
   // are faster (60 us per step against 69-86 us replayed: the graph's own inter-node gaps and the counter kernel).
-  // Not with r > 80 (no inverse tracking) or in profile mode (event pairs inside the GEMM).
-  const bool use_graph = ctx->sweep_graph && nt > 2 && r <= 80 && !ctx->profile;
+  // Not with r > 80 (no inverse tracking), in profile mode (event pairs inside the GEMM) or in GMRES mode.
+  const bool use_graph = ctx->sweep_graph && nt > 2 && r <= 80 && !ctx->profile && !gmres;
   for (long step = 0; step < nt; ++step) {
     if (use_graph && step == 1) {
       const long one = 1;
@@ -480,7 +487,8 @@ extern "C" int rt_hrom_bdf_sweep(rt_ctx* ctx, const rt_hsweep_desc* d, double* u
     // two launches per step: the expansion GEMM and the solve, which forms the right-hand side, falls back to a
     // pivoted LU by itself where the tracked inverse fails, and closes the step (state, trajectory, next rows of G)
     const rt_advance adv = advance_args(step + 1);
-    rc = rt_newton_solve_batched(ctx, KN, Xinv, rhs, r, B, step > 0 ? 1 : 0, info, &rq, &adv);
+    rc = gmres ? rt_gmres_launch(ctx, KN, nullptr, rhs, r, B, &ctx->gmres_opts, nullptr, nullptr, gwork, &rq, &adv, true)
+               : rt_newton_solve_batched(ctx, KN, Xinv, rhs, r, B, step > 0 ? 1 : 0, info, &rq, &adv);
     if (rc == RT_OK) {
       RT_HIP_CHECK(ctx, hipGetLastError());
       continue;

@@ -249,6 +249,30 @@ def dense_solve(K: torch.Tensor, b: torch.Tensor):
     return (bw[0] if single else bw), info
 
 
+def gmres_solve(K: torch.Tensor, b: torch.Tensor, opts=None):
+    """``scipy.sparse.linalg.gmres(K, b, **opts)`` on the device (rt_gmres_batched): restarted GMRES from x0 = 0 with
+    SciPy's stopping decisions, for K [r,r] or [B,r,r] (r <= 128) and b [r] or [B,r].  ``opts``: SciPy's keywords as
+    ``romtime_amd.gmres.gmres_opts`` reads them (None: SciPy's defaults).  Returns (x, info, iters) - SciPy's info (0, or
+    maxiter when the tolerance was not met) and the inner iterations per system, scalars for a single system.  Inputs
+    are not modified."""
+    from .gmres import gmres_opts
+
+    ctx = Context.current()
+    single = K.dim() == 2
+    Kw = K.reshape(-1, K.shape[-2], K.shape[-1]).contiguous()
+    bw = b.reshape(Kw.shape[0], -1).contiguous()
+    B, r, c = Kw.shape
+    if c != r or bw.shape[1] != r or Kw.dtype != torch.float64 or bw.dtype != torch.float64:
+        raise RomtimeHipError("gmres_solve: K must be float64 [r,r] / [B,r,r] and b float64 [r] / [B,r]")
+    o = gmres_opts(opts, r)
+    x = torch.empty_like(bw)
+    info = torch.empty(B, dtype=torch.int64, device=K.device)
+    iters = torch.empty(B, dtype=torch.int32, device=K.device)
+    ctx.check(ctx.lib.rt_gmres_batched(ctx.handle, _ptr(Kw), _ptr(bw), _ptr(x), r, B, C.byref(o), _ptr(info), _ptr(iters)),
+              "rt_gmres_batched")
+    return (x[0], info[0], iters[0]) if single else (x, info, iters)
+
+
 def dense_solve_multi(K: torch.Tensor, B: torch.Tensor):
     """X with K X = B for an r x r matrix (r <= 128) and r x nrhs right-hand sides.  Returns (X, info).
     rt_dense_solve_multi."""

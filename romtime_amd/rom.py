@@ -5,7 +5,8 @@ algebra on the MI355X.
   * ``to_rom``:  A_N = V^T (A V),  f_N = V^T f            -> rt_project_csr / rt_gemm_tn
   * ``to_fom_vector``: u_h = V u_N                        -> rt_gemm_nn
   * reduced solve (the reference's GMRES(20) on a dense r x r system, rom.py:36,492)
-                                                          -> rt_dense_solve_batched (pivoted LU)
+                                                          -> rt_dense_solve_batched (pivoted LU), or with
+                                                             REDUCED_SOLVER = "gmres" rt_gmres_batched
   * hyper-reduced operators                               -> the (M)DEIM classes
 The reduced basis V lives on the device for the whole online loop; the FOM callbacks
 (FEniCS or any duck type) stay on the host, so one time step moves each assembled
@@ -22,6 +23,7 @@ import torch
 
 from . import ops
 from .base import Reductor
+from .gmres import gmres_opts
 from .conventions import BDF, OperatorType, PistonParameters, RomParameters, Stage, Treewalk, TreewalkNonlinear
 from .storage import RomSolutionsStorage
 from .utils import CsrPattern, bilinear_to_csr, function_to_array, functional_to_array, is_matrix_like
@@ -39,7 +41,11 @@ _HYPER_SLOTS = {
 
 
 class RomConstructor(Reductor):
-    # kept for callers that read it; the device solve is direct and needs no tolerances
+    # The solver of the online loop's reduced systems, read at setup().  "direct": pivoted LU on the device, the exact
+    # solution of every system.  "gmres": the reference's own solver, scipy.sparse.linalg.gmres(K_N, b_N, **GMRES_OPTIONS)
+    # (rom.py:36,414-425,492), on the device with SciPy's stopping decisions: what reproduces trajectories the reference
+    # produced.  The two answers differ (by up to the GMRES tolerance), so the caller chooses.
+    REDUCED_SOLVER = "direct"
     GMRES_OPTIONS = dict(atol=1e-10, tol=1e-10, maxiter=1e6)
 
     def __init__(self, fom, grid, name=None) -> None:
@@ -113,6 +119,8 @@ class RomConstructor(Reductor):
     def truncate(self, n):
         """ROM with the last ``n`` basis vectors removed (S-ROM -> ROM, rom.py:169-198)."""
         truncated = self.__class__(fom=self.fom, grid=self.grid, name=self.name)
+        truncated.REDUCED_SOLVER = self.REDUCED_SOLVER
+        truncated.GMRES_OPTIONS = deepcopy(self.GMRES_OPTIONS)
         truncated.setup(rnd=self.random_state)
         N = self.N
         assert n < N, "You want to remove too many modes from S-ROM to create ROM."
@@ -216,8 +224,21 @@ class RomConstructor(Reductor):
 
     # ---- online (rom.py:414-555) ----------------------------------------------------------
     def create_algebraic_solver(self):
-        """``solver(A=K_N, b=b_N) -> (u_N, info)`` like the partial(gmres) of rom.py:414-425;
-        direct pivoted-LU on the device, ``info`` = 0 or 2 (singular pivot)."""
+        """``solver(A=K_N, b=b_N) -> (u_N, info)`` like the partial(gmres, **GMRES_OPTIONS) of rom.py:414-425.
+        REDUCED_SOLVER "direct": pivoted LU on the device, ``info`` = 0 or 2 (singular pivot); "gmres": restarted GMRES on
+        the device with the options as they are now, ``info`` as SciPy's (0, or maxiter)."""
+        if self.REDUCED_SOLVER == "gmres":
+            options = dict(self.GMRES_OPTIONS)
+            gmres_opts(options, 1)   # an unknown or unsupported key raises here, not in the online loop
+
+            def gmres_solver(A, b):
+                dev = isinstance(A, torch.Tensor)
+                x, info, _iters = ops.gmres_solve(ops.to_device(A), ops.to_device(b), options)
+                return (x if dev else x.cpu().numpy()), int(info)
+
+            return gmres_solver
+        if self.REDUCED_SOLVER != "direct":
+            raise ValueError(f"REDUCED_SOLVER must be 'direct' or 'gmres', not {self.REDUCED_SOLVER!r}")
 
         def solver(A, b):
             dev = isinstance(A, torch.Tensor)

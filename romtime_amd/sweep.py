@@ -8,22 +8,55 @@ assembly (or an MDEIM expansion in FOM coordinates) provides; the coefficient ta
 evaluated on the host for all (step, mu) beforehand and uploaded once."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import numpy as np
 import torch
 
 from . import ops
-from ._lib import Context, SweepDesc
+from ._lib import SOLVER_DIRECT, SOLVER_GMRES, Context, SweepDesc
 
 _p = C.c_void_p
 
 
-def rom_bdf_sweep(V, indptr, indices, mass, terms, term_coef, tril, rhs_terms, rhs_coef, dt, bdf2=True):
+@contextlib.contextmanager
+def reduced_solver(ctx, solver, gmres_options, r):
+    """Inside the block the sweeps on ``ctx`` solve their reduced systems with ``solver``: "direct" (tracked inverse /
+    pivoted LU, the exact solution) or "gmres" (the reference's restarted GMRES with ``gmres_options``, None =
+    ``RomConstructor.GMRES_OPTIONS``).  The ctx's previous solver is restored afterwards, also on error."""
+    from .gmres import gmres_opts
+
+    if solver == "gmres":
+        if gmres_options is None:
+            from .rom import RomConstructor
+
+            gmres_options = RomConstructor.GMRES_OPTIONS
+        want = (SOLVER_GMRES, gmres_opts(gmres_options, r))
+    elif solver == "direct":
+        if gmres_options is not None:
+            raise ValueError("gmres_options given with solver='direct'")
+        want = (SOLVER_DIRECT, None)
+    else:
+        raise ValueError(f"solver must be 'direct' or 'gmres', not {solver!r}")
+    prev = ctx.reduced_solver
+    if want[0] == prev[0] == SOLVER_DIRECT:
+        yield
+        return
+    ctx.set_reduced_solver(*want)
+    try:
+        yield
+    finally:
+        ctx.set_reduced_solver(*prev)
+
+
+def rom_bdf_sweep(V, indptr, indices, mass, terms, term_coef, tril, rhs_terms, rhs_coef, dt, bdf2=True, solver="direct",
+                  gmres_options=None):
     """Returns the reduced trajectories ``uN`` as a (n_mu, nt, r) CUDA tensor.
 
     V (N x r); indptr/indices CSR pattern; mass (nnz); terms (Q x nnz); term_coef (nt x n_mu x Q);
-    tril (nnz) or None; rhs_terms (F x N); rhs_coef (nt x n_mu x F)."""
+    tril (nnz) or None; rhs_terms (F x N); rhs_coef (nt x n_mu x F).  ``solver``: "direct" (default) or "gmres" with
+    ``gmres_options`` (``reduced_solver``)."""
     ctx = Context.current()
     Vd = ops.to_device(np.ascontiguousarray(V) if isinstance(V, np.ndarray) else V).contiguous()
     N, r = Vd.shape
@@ -39,11 +72,12 @@ def rom_bdf_sweep(V, indptr, indices, mass, terms, term_coef, tril, rhs_terms, r
                      n_terms=0 if terms_d is None else terms_d.shape[0], term_values=ptr(terms_d), term_coef=ptr(tcoef_d),
                      tril_values=ptr(tril_d), n_rhs=0 if rhs_d is None else rhs_d.shape[0], rhs_terms=ptr(rhs_d),
                      rhs_coef=ptr(rcoef_d))
-    ctx.check(ctx.lib.rt_rom_bdf_sweep(ctx.handle, C.byref(desc), _p(out.data_ptr())), "rt_rom_bdf_sweep")
+    with reduced_solver(ctx, solver, gmres_options, r):
+        ctx.check(ctx.lib.rt_rom_bdf_sweep(ctx.handle, C.byref(desc), _p(out.data_ptr())), "rt_rom_bdf_sweep")
     return out
 
 
-def hrom_bdf_sweep(mass, lin, nl, rhs, dt, bdf2=True):
+def hrom_bdf_sweep(mass, lin, nl, rhs, dt, bdf2=True, solver="direct", gmres_options=None):
     """Hyper-reduced online sweep on the device (``rt_hrom_bdf_sweep``): the time loop of
     ``RomConstructor*.solve`` with every reduced operator obtained by (M)DEIM interpolation,
     ``interpolate(which=ROM)`` (deim.py:416-452, mdeim.py:230-261), for all parameter points at once.
@@ -54,7 +88,8 @@ def hrom_bdf_sweep(mass, lin, nl, rhs, dt, bdf2=True):
     parameter point (what ``assemble(mu, t, entries=dofs)`` returns).  ``nl``: None or a dict with ``PT_U``,
     ``basis_rom``, ``W`` (m x r), optional ``C`` (nt x n_mu x m) and ``S`` (nt x n_mu): entries = S (W u_N* + C).
     The theta solve is folded into the expansion once (Z = basis_rom PT_U^-1); the loop then never touches anything
-    of size N_h.  Returns ``uN`` (n_mu, nt, r) as a CUDA tensor."""
+    of size N_h.  ``solver``: "direct" (default) or "gmres" with ``gmres_options`` (``reduced_solver``).  Returns ``uN``
+    (n_mu, nt, r) as a CUDA tensor."""
     from ._lib import HSweepDesc
 
     ctx = Context.current()
@@ -98,7 +133,8 @@ def hrom_bdf_sweep(mass, lin, nl, rhs, dt, bdf2=True):
     desc = HSweepDesc(r=r, n_mu=n_mu, nt=nt, dt=float(dt), bdf2=int(bool(bdf2)), m_mass=m_mass, m_lin=m_lin, m_nl=m_nl,
                       m_rhs=m_rhs, Z=ptr(Z), Zf=ptr(Zf), F_mass=ptr(Fm), F_lin=ptr(Fl), F_rhs=ptr(Ff), W=ptr(W),
                       C_nl=ptr(Cn), S_nl=ptr(Sn))
-    ctx.check(ctx.lib.rt_hrom_bdf_sweep(ctx.handle, C.byref(desc), _p(out.data_ptr())), "rt_hrom_bdf_sweep")
+    with reduced_solver(ctx, solver, gmres_options, r):
+        ctx.check(ctx.lib.rt_hrom_bdf_sweep(ctx.handle, C.byref(desc), _p(out.data_ptr())), "rt_hrom_bdf_sweep")
     return out
 
 
