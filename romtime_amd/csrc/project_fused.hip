@@ -98,7 +98,10 @@ struct ProjParams {
   int N, k_per_split;
   int r, B, S;
   int flags;
-  int xcd_map;          // 1: workgroups of an XCD take a contiguous run of the range-major work list (see the kernel)
+  // 1 (always): workgroups of an XCD take a contiguous run of the range-major work list (see the kernel).  The round-robin
+  // branch is unreachable; it stays for now because the kernel's code generation is touchy: with the field and the branch
+  // folded away the <5, false> instantiation measured 0.3-1 % slower (profiles/env_switch_removal_ab.txt).
+  int xcd_map;
   const StageRec* rec;  // [stages]; handed to the kernel as an argument of its own (see project_fused_kernel)
   const int* any_unwindowed;
 };
@@ -628,9 +631,8 @@ int rt_project_fused(rt_ctx* ctx, const int64_t* indptr, const int64_t* indices,
     }
     RT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   }
-  static const int xcd_map = [] { const char* e = getenv("ROMTIME_PROJECT_MAP"); return e ? atoi(e) : 1; }();
-  p.xcd_map = xcd_map;
-  const unsigned grid = xcd_map ? (unsigned)(((B * S + 7) / 8) * 8) : (unsigned)(B * S);
+  p.xcd_map = 1;
+  const unsigned grid = (unsigned)(((B * S + 7) / 8) * 8);   // whole eighths of the work list, one per XCD
   switch (tr) {
     case 1: rc = launch_fused<1>(ctx, p, grid, banded); break;
     case 2: rc = launch_fused<2>(ctx, p, grid, banded); break;

@@ -212,15 +212,14 @@ void launch_skinny_tn(hipStream_t st, dim3 grid, int threads, const double* A, l
 // C (m x n, row-major, ldc) = A^T B for row-major A (N x m), B (N x n), m <= 16, N long; RT_ERR_UNSUPPORTED otherwise.
 int rt_skinny_tn(rt_ctx* ctx, const double* A, int64_t lda, const double* B, int64_t ldb, int64_t N, int64_t m, int64_t n,
                  double* Cm, int64_t ldc) {
-  static const int flags = [] { const char* e = getenv("ROMTIME_DEFLATE_FLAGS"); return e ? atoi(e) : 0; }();
-  if ((flags & 1) || m > ST_MMAX || n > 4096 || N < 16384 || N * n < (1L << 22)) return RT_ERR_UNSUPPORTED;
+  if (m > ST_MMAX || n > 4096 || N < 16384 || N * n < (1L << 22)) return RT_ERR_UNSUPPORTED;
   const int pairs = (int)((n + 1) / 2);
   const int threads = pairs >= 256 ? 256 : ((pairs + 63) / 64) * 64;
   const unsigned gy = (unsigned)((pairs + threads - 1) / threads);
   const long waves = (long)(threads / 64) * gy;
   // four waves per SIMD (the register budget of m = 16 allows no more): 5.7 TB/s on 1e6 x 512 with m = 8 against 4.7 with two;
   // but no more slabs than a sixteenth of B's bytes
-  long gx = (long)ctx->num_cus * ((flags & 2) ? 8 : (flags & 4) ? 32 : 16) / waves;
+  long gx = (long)ctx->num_cus * 16 / waves;
   if (gx > N / (16 * m)) gx = N / (16 * m);
   if (gx < 1) gx = 1;
   long rows_per_wg = (N + gx - 1) / gx;

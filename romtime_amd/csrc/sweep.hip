@@ -9,8 +9,6 @@
 //   u_h[b] = V u^{n+1}[b],   u* = 2 u_h - u_h^{n-1}                          next step's trilinear state
 // The operators are affine in precomputed value vectors on one CSR pattern (the form MDEIM itself
 // produces, and what a closed-form 1-D assembly yields); the state-dependent term is diag(u*) T.
-#include <cstdlib>
-
 #include "common.h"
 #include "sweep_advance.h"
 
@@ -30,11 +28,9 @@ constexpr int EX_KP = 144, EX_SA = EX_KP + 2, EX_SB = 34, EX_THREADS = 256;
 constexpr int EX_LA = 64 * EX_KP / 2 / EX_THREADS;   // d2 loads of G per thread and phase (18)
 constexpr int EX_LB = EX_KP * 32 / 2 / EX_THREADS;   // d2 loads of Z per thread and phase (9)
 
-template <int MODE>   // 0; timing ablations (ROMTIME_SWEEP_FLAGS, results wrong): 6 = no global loads, 8 = one k-step, 14 = both
 __global__ __launch_bounds__(EX_THREADS) void expansion_kernel(const double* __restrict__ G, long ldg,
                                                                 const double* __restrict__ Z, long ldz,
                                                                 double* __restrict__ Cm, long ldc, int R, int K, long N) {
-  constexpr int mode = MODE;
   extern __shared__ __attribute__((aligned(16))) double ex_sm[];
   double* sA = ex_sm;                    // [64][EX_SA]: G rows, contraction contiguous
   double* sB = ex_sm + 64 * EX_SA;       // [EX_KP][EX_SB]: Z rows of this tile's 32 columns
@@ -55,7 +51,7 @@ __global__ __launch_bounds__(EX_THREADS) void expansion_kernel(const double* __r
       const int k = k0 + kk;
       const bool ok = row < R && k < K;
       const long off = (long)(row < R ? row : R - 1) * ldg + (k < K ? k : K - 2);
-      const xd2 v = (mode & 2) ? xd2{1.0, 1.0} : *reinterpret_cast<const xd2*>(G + off);
+      const xd2 v = *reinterpret_cast<const xd2*>(G + off);
       ra[i] = ok ? v : xd2{0.0, 0.0};
     }
 #pragma unroll
@@ -64,7 +60,7 @@ __global__ __launch_bounds__(EX_THREADS) void expansion_kernel(const double* __r
       const int k = k0 + kk;
       const bool ok = k < K && n0 + j < N;
       const long off = (long)(k < K ? k : K - 1) * ldz + (n0 + j < N ? n0 + j : N - 2);
-      const xd2 v = (mode & 4) ? xd2{1.0, 1.0} : *reinterpret_cast<const xd2*>(Z + off);
+      const xd2 v = *reinterpret_cast<const xd2*>(Z + off);
       rb[i] = ok ? v : xd2{0.0, 0.0};
     }
   };
@@ -88,7 +84,7 @@ __global__ __launch_bounds__(EX_THREADS) void expansion_kernel(const double* __r
     __syncthreads();
     if (k0 + EX_KP < K) fetch(k0 + EX_KP);   // the next phase's loads fly while this one is multiplied
 #pragma unroll
-    for (int k4 = 0; k4 < ((mode & 8) ? 2 : EX_KP / 4); ++k4) {
+    for (int k4 = 0; k4 < EX_KP / 4; ++k4) {
       const double a = fa[4 * k4];
       const double b0 = fb[4 * k4 * EX_SB], b1 = fb[4 * k4 * EX_SB + 16];
       acc[0][k4 & 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b0, acc[0][k4 & 1], 0, 0, 0);
@@ -111,26 +107,13 @@ __global__ __launch_bounds__(EX_THREADS) void expansion_kernel(const double* __r
 // C = G Z for R <= 64 rows; RT_ERR_UNSUPPORTED beyond (the caller takes the generic GEMM).
 int rt_expansion_gemm(rt_ctx* ctx, const double* G, long ldg, const double* Z, long ldz, double* Cm, long ldc, long R,
                       long K, long N) {
-  static const int flags = [] { const char* e = getenv("ROMTIME_SWEEP_FLAGS"); return e ? atoi(e) : 0; }();
-  const bool off = flags & 1;
-  if (off || R > 64 || R < 1 || K < 2 || N < 2 || ((K | N | ldg | ldz) & 1) ||
+  if (R > 64 || R < 1 || K < 2 || N < 2 || ((K | N | ldg | ldz) & 1) ||
       ((reinterpret_cast<size_t>(G) | reinterpret_cast<size_t>(Z)) & 15))
     return RT_ERR_UNSUPPORTED;
   const size_t lds = sizeof(double) * (64 * EX_SA + EX_KP * EX_SB);
   const dim3 grid((unsigned)((N + 31) / 32));
-#define EX_LAUNCH(M_)                                                                                              \
-  {                                                                                                                \
-    RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&expansion_kernel<M_>), (int)lds));                      \
-    hipLaunchKernelGGL(expansion_kernel<M_>, grid, dim3(EX_THREADS), lds, ctx->stream, G, ldg, Z, ldz, Cm, ldc, (int)R, \
-                       (int)K, N);                                                                                 \
-  }
-  switch (flags & 14) {
-    case 6: EX_LAUNCH(6) break;
-    case 8: EX_LAUNCH(8) break;
-    case 14: EX_LAUNCH(14) break;
-    default: EX_LAUNCH(0) break;
-  }
-#undef EX_LAUNCH
+  RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&expansion_kernel), (int)lds));
+  hipLaunchKernelGGL(expansion_kernel, grid, dim3(EX_THREADS), lds, ctx->stream, G, ldg, Z, ldz, Cm, ldc, (int)R, (int)K, N);
   RT_HIP_CHECK(ctx, hipGetLastError());
   ctx->last_grid = grid.x; ctx->last_splits = 1; ctx->last_tile = 64 * 1000 + 32;
   return RT_OK;

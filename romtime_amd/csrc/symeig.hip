@@ -18,8 +18,6 @@
 //      four per reduction round.
 // The caller (pod.py) adds a k x k Rayleigh-Ritz step on G when kept eigenvalues are clustered, which also
 // cross-checks the Ritz values against the multisection eigenvalues; a mismatch raises (nothing silent).
-#include <cstdlib>
-
 #include "common.h"
 #include "wave_ops.h"
 
@@ -699,20 +697,15 @@ extern "C" int rt_sym_eig_values_part(rt_ctx* ctx, const double* G, int64_t n, i
     return RT_ERR_UNSUPPORTED;
   }
   const bool large = n > 512;
-  static const int eig_flags = [] { const char* e = getenv("ROMTIME_EIG_FLAGS"); return e ? atoi(e) : 0; }();
   // A ctx confined to few CUs (CU-masked stream of the POD pipeline, "cu_limit") halves the team for n <= 512: 16
   // workgroups hold 32 rows each (147 KB of LDS); a column then costs more mat-vec but the same hand-off.
   const bool small_team = !large && ctx->num_cus < TW_SMALL && ctx->num_cus >= TW_SMALL / 2;
-  static const int tw_env = [] { const char* e = getenv("ROMTIME_EIG_TW"); return e ? atoi(e) : 0; }();   // measurement switch
   int tw = large ? TW_LARGE : (small_team ? TW_SMALL / 2 : TW_SMALL);
-  if (!large && tw_env >= 1 && tw_env <= TW_SMALL && (long)((n + tw_env - 1) / tw_env) * n * 8 <= 120 * 1024) tw = tw_env;
-  // One workgroup holds the whole matrix: no hand-offs (see the kernel).  Measured (tools/probes/eig_tw_ab.py, values + 40
-  // vectors): n = 16 / 33 / 64: 0.076 / 0.120 / 0.211 ms against 0.091 / 0.140 / 0.233 in the cooperative form - but
+  // One workgroup holds the whole matrix: no hand-offs (see the kernel).  Measured (values + 40 vectors): n = 16 / 33 / 64: 0.076 / 0.120 / 0.211 ms against 0.091 / 0.140 / 0.233 in the cooperative form - but
   // n = 128: 0.50 against 0.44: the hand-off is NOT what a column costs at these sizes (nor does the team size matter:
   // 32, 16, 8, 2 or 1 workgroups give the same 3.3 us per column); it is the three barriers of a 1024-thread workgroup and
-  // wave 0's serial sections, and with all 128 rows in one workgroup those get longer.  ROMTIME_EIG_FLAGS & 8 extends the
-  // form to n <= 128 for measurements.
-  const bool local = (n <= 64 || ((eig_flags & 8) && n <= 128)) && !(eig_flags & 4);
+  // wave 0's serial sections, and with all 128 rows in one workgroup those get longer.  So the form stops at n = 64.
+  const bool local = n <= 64;
   if (local) tw = 1;
   if (tw > ctx->num_cus) {  // the cooperating workgroups must all be resident
     ctx->err = "rt_sym_eig_values: not enough compute units for the cooperative tridiagonalisation";
@@ -731,8 +724,8 @@ extern "C" int rt_sym_eig_values_part(rt_ctx* ctx, const double* G, int64_t n, i
   tp.G = G; tp.n = (int)n; tp.tw = tw;
   // n <= 512: launch 16 x 32 blocks, of which the first 32 that find themselves on XCD eig_xcd work, so the 32
   // workers can hand off through one L2 (the kernel checks HW_REG_XCC_ID and falls back to the general form).
-  // ROMTIME_EIG_FLAGS=1 disables it.
-  tp.spread = (!large && !local && ctx->eig_one_xcd && !(eig_flags & 1) && ctx->num_cus / 8 >= tw) ? 1 : 0;  // a CU per worker
+  // The ctx option "eig_one_xcd" turns it off.
+  tp.spread = (!large && !local && ctx->eig_one_xcd && ctx->num_cus / 8 >= tw) ? 1 : 0;  // a CU per worker
   tp.local = local ? 1 : 0;
   tp.xcd = ctx->eig_xcd & 7;
   tp.V = reinterpret_cast<double*>(b8 + oV); tp.P = reinterpret_cast<double*>(b8 + oP);
@@ -746,8 +739,7 @@ extern "C" int rt_sym_eig_values_part(rt_ctx* ctx, const double* G, int64_t n, i
   const size_t lds = sizeof(double) * ((size_t)RB * (local ? n + 2 : n) + 5 * n + 16);  // A slab | v (x2) | w | row | p (local form)
   // n <= 256 has instantiations of its own (round 3): wave 0's register work per column - reflector, w, the updated row:
   // NM / 64 elements per lane - and the eigenvector kernel's back-transformation halve against the 512 ones
-  static const bool small_nm = !(eig_flags & 2);
-  const bool tiny = small_nm && n <= 256, tinier = small_nm && n <= 128;
+  const bool tiny = n <= 256, tinier = n <= 128;
   RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&symeig_tridiag_kernel<128>), 150 * 1024));
   RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&symeig_tridiag_kernel<256>), 150 * 1024));
   RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&symeig_tridiag_kernel<512>), 150 * 1024));
@@ -811,7 +803,6 @@ extern "C" int rt_sym_eig_vectors(rt_ctx* ctx, int64_t n, int64_t k, const doubl
   int rc = rt_scratch(ctx, sizeof(double) * 6 * (size_t)nblk, &cbuf);  // leaf arena: free between the two calls
   if (rc != RT_OK) return rc;
   vp.C = static_cast<const double*>(cbuf);
-  static const int eig_flags_v = [] { const char* e = getenv("ROMTIME_EIG_FLAGS"); return e ? atoi(e) : 0; }();
   RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&symeig_vectors_kernel<128>), 80 * 1024));
   RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&symeig_vectors_kernel<256>), 80 * 1024));
   RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&symeig_vectors_kernel<512>), 80 * 1024));
@@ -821,12 +812,12 @@ extern "C" int rt_sym_eig_vectors(rt_ctx* ctx, int64_t n, int64_t k, const doubl
     hipLaunchKernelGGL(symeig_wy_kernel<1024>, dim3((unsigned)nblk), dim3(64), 0, ctx->stream, vp.V, (int)n,
                        static_cast<double*>(cbuf));
     hipLaunchKernelGGL(symeig_vectors_kernel<1024>, dim3((unsigned)k), dim3(64), vlds, ctx->stream, vp);
-  } else if (n <= 128 && !(eig_flags_v & 2)) {
+  } else if (n <= 128) {
     const size_t vlds = sizeof(double) * (8 * 128 + 8) + 128;
     hipLaunchKernelGGL(symeig_wy_kernel<128>, dim3((unsigned)nblk), dim3(64), 0, ctx->stream, vp.V, (int)n,
                        static_cast<double*>(cbuf));
     hipLaunchKernelGGL(symeig_vectors_kernel<128>, dim3((unsigned)k), dim3(64), vlds, ctx->stream, vp);
-  } else if (n <= 256 && !(eig_flags_v & 2)) {
+  } else if (n <= 256) {
     const size_t vlds = sizeof(double) * (8 * 256 + 8) + 256;
     hipLaunchKernelGGL(symeig_wy_kernel<256>, dim3((unsigned)nblk), dim3(64), 0, ctx->stream, vp.V, (int)n,
                        static_cast<double*>(cbuf));

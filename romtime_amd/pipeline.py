@@ -93,9 +93,12 @@ atexit.register(shutdown)
 
 class PodPipeline:
     def __init__(self, eig_cus_per_xcd: int = 4, device=None, group=None, eig_first_cu: int = 0, gram_range=None,
-                 small_set=None):
+                 small_set=None, gram_pace: bool = False):
         """``eig_cus_per_xcd``: CUs of every XCD given to the eigensolver stream (4 -> 32 CUs: a CU per cooperating
         workgroup; 4 and 8 keep the shader engines of an XCD evenly loaded, other values measured slower).
+        ``gram_pace``: pace the Gram stream's workgroups (ctx option "gram_pace": L2 sharing between the tiles of an XCD).
+        Off by default: pacing costs nothing on the whole chip but 2 % on this stream's share of it (5.98 vs 5.87 ms per
+        POD, profiles/r03_gram_pace_ab.txt).
         ``group``: torch.distributed process group of a row-sharded run - the Gram matrices are summed over it on stream
         G (one all-reduce per snapshot set), the small eigenproblem is replicated on every rank (identical inputs,
         deterministic kernels: identical outputs).
@@ -126,9 +129,7 @@ class PodPipeline:
         self.ctxE.set_option("cu_limit", 8 * e)
         self.ctxE.set_option("eig_one_xcd", 0)       # the E CUs span all XCDs: write-through hand-off
         self.ctxG.set_option("cu_limit", 8 * g_count)
-        # the paced Gram (L2 sharing between the tiles of an XCD) costs nothing on the whole chip but 2 % on this stream's
-        # share of it (5.98 vs 5.87 ms per POD, tools/probes/pace_pipeline_ab.sh): off here unless asked for
-        self.ctxG.set_option("gram_pace", int(os.environ.get("ROMTIME_PIPELINE_GRAM_PACE", "0")))
+        self.ctxG.set_option("gram_pace", int(bool(gram_pace)))
         self.group = group
         # Row-sharded run: the small collectives of stream E (the broadcast of a set's eigen-results from the rank that
         # solved it) go through a process group of their own, so that they never queue behind the Gram all-reduce of the

@@ -89,3 +89,15 @@ def test_gram_plan_choice_is_host_logic_and_matches_the_measured_rules():
     assert plan(256, 200_000, 256)[0] == 2 and plan(256, 50_000, 512)[:3] == (2, 7, 5) and plan(256, 30_000, 384)[0] == 2
     assert plan(256, 1_000_000, 96)[0] == 0 and plan(256, 4000, 512)[0] == 0 and plan(256, 1_000_000, 1100)[0] == 0
     assert lib.rt_gram_plan_info(256, 0, 512, (C.c_int * 5)()) < 0
+
+
+def test_library_reads_no_environment_variable():
+    """The shipped library has no environment switches: what it computes and which kernels it runs depend on its
+    arguments and ctx options alone.  Its file holds no ROMTIME_ name, and getenv is not among the symbols it imports (a
+    name in the dynamic string table is a NUL-delimited string; the ROMTIME_PF_ABLATE timing build is a different file)."""
+    from romtime_amd import _lib
+
+    data = open(_lib.load()._name, "rb").read()
+    assert data[:4] == b"\x7fELF"
+    assert b"ROMTIME_" not in data
+    assert b"\0getenv\0" not in data

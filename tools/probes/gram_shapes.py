@@ -1,5 +1,5 @@
-"""Time of the snapshot Gram kernel over a few shapes (ROMTIME_GRAM_FLAGS / ROMTIME_GRAM_PACE from the environment) and
-its error against torch on a slice.   python3 tools/probes/gram_shapes.py"""
+"""Time of the snapshot Gram kernel over a few shapes and its error against torch on a slice.
+   python3 tools/probes/gram_shapes.py"""
 import os
 import sys
 
@@ -9,7 +9,6 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 from romtime_amd import ops  # noqa: E402
 from romtime_amd._lib import Context  # noqa: E402
 
-tag = os.environ.get("ROMTIME_GRAM_FLAGS", "-") + ":" + os.environ.get("ROMTIME_GRAM_PACE", "-")
 SHORT = [(100_000, 256, "C"), (100_000, 200, "C"), (50_000, 512, "C"), (30_000, 384, "C"), (200_000, 256, "C"), (100_000, 384, "C"),
          (60_000, 1000, "C"), (100_000, 256, "F"), (250_000, 200, "C")]
 for (N, n, order) in SHORT if "short" in sys.argv else [(1_000_000, 512, "C"), (1_000_000, 384, "C"), (1_000_000, 256, "C"), (600_000, 640, "C"),
@@ -29,6 +28,6 @@ for (N, n, order) in SHORT if "short" in sys.argv else [(1_000_000, 512, "C"), (
     torch.cuda.synchronize()
     ref = X[:, :8].T @ X
     info = Context.current().launch_info()
-    print(f"{tag} N={N} n={n} {order}: {e0.elapsed_time(e1) / 20:.3f} ms  grid {info['grid']} splits {info['splits']}  "
+    print(f"N={N} n={n} {order}: {e0.elapsed_time(e1) / 20:.3f} ms  grid {info['grid']} splits {info['splits']}  "
           f"err {float((G[:8] - ref).abs().max() / ref.abs().max()):.1e}  sym {bool(torch.equal(G, G.T))}", flush=True)
     del X, G, ref
