@@ -297,6 +297,22 @@ int rt_hrom_bdf_sweep(rt_ctx* ctx, const rt_hsweep_desc* desc, double* uN_out);
  * K^T/(|K|_1 |K|_inf), systems handed to the pivoted LU, systems solved }.  Synchronises the ctx stream. */
 int rt_last_sweep_stats(rt_ctx* ctx, int64_t* stats4);
 
+/* ---- error certification of whole trajectories (compute_error per time step, rom/base.py:52-73; the S-ROM estimator
+ *      compute_rom_difference, utils.py:173-212; the three curves of HyperReducedPiston._evaluate, hrom.py:546-582) ---- */
+/* err[j][t] = || U_j[:, t] - B a_j[t] ||_2 / sqrt(N) and ref[j][t] = || U_j[:, t] ||_2 / sqrt(N) for n_traj trajectories
+ * and nt steps each, the lifted trajectory B a never stored.  B: N x k row-major basis (ldb), k <= 128 (RT_ERR_UNSUPPORTED
+ * beyond).  A: coefficients, trajectory j is the nt x k row-major matrix (lda) at A + j * stride_a - with lda = r and
+ * stride_a = nt * r exactly the uN_out of the sweeps above.  U: full-order snapshots, trajectory j the N x nt matrix
+ * (ldu, u_layout) at U + j * stride_u; RT_COL_MAJOR = every snapshot contiguous (np.vstack(cols).T).  U == NULL: the
+ * term is absent and err is the estimator || B a_t || / sqrt(N) (ref must then be NULL: RT_ERR_ARG, as for sizes < 1).
+ * err, ref (may be NULL): n_traj x nt.  Any leading dimensions, 8-byte aligned bases.  No floating-point atomics: the
+ * sums run in a fixed order that depends on N, nt and the ctx's CU count only, so a trajectory's bits depend neither on
+ * n_traj nor on its place in the batch; sqrt and the division are the correctly rounded IEEE operations.  Scratch from the
+ * ctx's leaf arena; rt_last_launch_info: [0] workgroups, [1] row slices, [2] tile 32 rows x 64 steps. */
+int rt_trajectory_errors(rt_ctx* ctx, const double* B, int64_t ldb, const double* A, int64_t lda, int64_t stride_a,
+                         const double* U, int64_t ldu, int u_layout, int64_t stride_u, int64_t N, int64_t k, int64_t nt,
+                         int64_t n_traj, double* err, double* ref);
+
 /* ---- closed-form local assembly of the 1-D P1 operators at (M)DEIM entries (the step before the path) ----------
  * What ``assemble(mu, t, entries=dofs[, u_n])`` returns for the reference's 1-D problems (fom/base.py:523-599 per-entry
  * assembly of the forms in fom/nonlinear.py:374-494; closed forms as in testing/mock.py:30-85), for n_states states at

@@ -158,6 +158,56 @@ def gemm_nn(X: torch.Tensor, T: torch.Tensor, out: torch.Tensor = None, alpha: f
     return Y
 
 
+def _layout_last2(t: torch.Tensor):
+    """(ld, layout) of the trailing two dimensions of a float64 CUDA tensor, or None where neither has unit stride."""
+    r, c = t.shape[-2:]
+    s0, s1 = t.stride()[-2:]
+    if s1 == 1 and (s0 >= c or r == 1):
+        return max(s0, c), ROW_MAJOR
+    if s0 == 1 and (s1 >= r or c == 1):
+        return max(s1, r), COL_MAJOR
+    return None
+
+
+def trajectory_errors(B: torch.Tensor, A: torch.Tensor, U: torch.Tensor = None, want_ref: bool = False):
+    """err[j, t] = ||U_j[:, t] - B A_j[t, :]||_2 / sqrt(N) without storing the lifted trajectories B A_j^T
+    (rt_trajectory_errors).  B: N x k basis (k <= 128); A: (nt, k) or (n, nt, k) coefficients, as the sweeps return
+    them; U: None (then err = ||B A_j[t]|| / sqrt(N), the estimator), an N x nt matrix or (n, N, nt), either memory
+    order.  Returns err (n, nt), and with ``want_ref`` also ref[j, t] = ||U_j[:, t]||_2 / sqrt(N)."""
+    ctx = Context.current()
+    for name, t in (("B", B), ("A", A), ("U", U)):
+        if t is not None and (t.dtype != torch.float64 or not t.is_cuda):
+            raise RomtimeHipError(f"trajectory_errors: {name} must be a float64 CUDA tensor")
+    if B.dim() != 2 or A.dim() not in (2, 3) or (U is not None and U.dim() not in (2, 3)):
+        raise RomtimeHipError("trajectory_errors: B must be 2-D, A and U 2-D or 3-D")
+    if want_ref and U is None:
+        raise RomtimeHipError("trajectory_errors: the reference norms are those of U")
+    if A.dim() == 2:
+        A = A.unsqueeze(0)
+    if U is not None and U.dim() == 2:
+        U = U.unsqueeze(0)
+    N, k = B.shape
+    n, nt, k2 = A.shape
+    if k2 != k or (U is not None and tuple(U.shape) != (n, N, nt)):
+        raise RomtimeHipError(f"trajectory_errors: shapes do not match (B {tuple(B.shape)}, A {tuple(A.shape)}, "
+                              f"U {None if U is None else tuple(U.shape)})")
+    if _layout_last2(B) is None or _layout_last2(B)[1] != ROW_MAJOR:
+        B = B.contiguous()
+    if _layout_last2(A) is None or _layout_last2(A)[1] != ROW_MAJOR:
+        A = A.contiguous()
+    ldb, lda = _layout_last2(B)[0], _layout_last2(A)[0]
+    ldu, lu, su = 0, ROW_MAJOR, 0
+    if U is not None:
+        if _layout_last2(U) is None:
+            U = U.contiguous()
+        (ldu, lu), su = _layout_last2(U), U.stride(0)
+    err = torch.empty((n, nt), dtype=torch.float64, device=B.device)
+    ref = torch.empty((n, nt), dtype=torch.float64, device=B.device) if want_ref else None
+    ctx.check(ctx.lib.rt_trajectory_errors(ctx.handle, _ptr(B), ldb, _ptr(A), lda, A.stride(0), _ptr(U), ldu, lu, su, N, k, nt,
+                                           n, _ptr(err), _ptr(ref)), "rt_trajectory_errors")
+    return (err, ref) if want_ref else err
+
+
 def rank_update(Ysrc: torch.Tensor, X: torch.Tensor, T: torch.Tensor, alpha: float = -1.0, colscale: torch.Tensor = None,
                 out: torch.Tensor = None) -> torch.Tensor:
     """``out = Ysrc diag(colscale) + alpha X T`` for a tall row-major Ysrc (N x n), thin X (N x k) and T (k x n);
