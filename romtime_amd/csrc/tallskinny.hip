@@ -1,14 +1,27 @@
 // Tall-skinny product  Y (N x k) = X (N x n, row-major) T (n x k),  k <= 128: the POD back-projection
 // U_r = X W (pod.py:38 folded into the Gram route, SURVEY 8d "POD pass 2") and the lift u_h = V u_N.
 //
-// 8 N (n + k) bytes for 2 N n k flops: at k = 40 (three 16-wide MFMA column tiles) the matrix-core time is
-// within 15 % of the HBM time, so the kernel is built to overlap the two as well as possible rather than for
-// either alone: a workgroup takes 64 rows and walks the contraction in stages of 32 columns (256 contiguous
-// bytes per row), X and T stages go HBM -> registers -> LDS (next stage in flight while the current one is
-// multiplied), 4 waves x 16 rows, each wave all ceil(k/16) column tiles; 29 KB of LDS and <= 128 VGPRs leave room
-// for four workgroups per CU.  Measured 4.1 TB/s at 1e6 x 512 -> 40 (generic skinny tile: 3.8; 64-column stages
-// with two workgroups per CU: 3.8).  A form that fed X to the MFMAs straight from registers, never through LDS, measured
-// slower (1.095 vs 1.04 ms) and non-temporal loads of X / stores of Y changed nothing: profiles/r03_tallskinny_ab.txt.
+// 8 N (n + k) bytes for 2 N n k flops: at k = 40 the matrix-core time is within 15 % of the HBM time, so the kernel is
+// built to overlap the two as well as possible rather than for either alone: a workgroup takes 64 rows and walks the
+// contraction in stages of 32 columns (256 contiguous bytes per row), X and T stages go HBM -> registers -> LDS (next
+// stage in flight while the current one is multiplied), 4 waves x 16 rows, each wave all output columns; 29 KB of LDS and
+// <= 128 VGPRs leave room for four workgroups per CU.
+//
+// Output columns: k / 16 full tiles through v_mfma_f64_16x16x4_f64, and a remainder of 1 .. 12 columns through
+// v_mfma_f64_4x4x4_4b_f64, one instruction per group of four columns: its four blocks are rows 4 b .. 4 b + 3 of the
+// 16-row block against the same four columns of T, its A operand is the 16x16x4 A operand lane for lane, its B operand
+// one more ds_read_b64 per group and k-step.  On gfx950 the four-block form runs at the flop rate of the 16x16x4 form
+// (0.164 of its time per instruction on a chip that issues nothing else, 0.25 in cycles; lane maps and rate:
+// profiles/r05_mfma_f64_blocks.txt), so 8 remainder columns cost 32 matrix-core cycles per block and k-step where a
+// zero-padded third tile cost 64: at k = 40 the kernel issues 5/6 of the matrix-core cycles it did, which on the POD
+// pipeline's 224 CUs is what bounds it (0.84 ms of 16x16x4 cycles against a 0.74 ms HBM floor before, 0.70 ms now).
+// A remainder of 13 .. 15 columns stays a zero-padded tile (four groups would cost the same).  T is staged only up to
+// the next multiple of four columns; the LDS stride of a T row stays 16 ceil(k / 16).
+// Measured at 1e6 x 512 -> 40 on the whole chip: 0.94 ms = 4.7 TB/s (padded third tile: 0.99 ms; generic skinny tile
+// 3.8 TB/s; 64-column stages with two workgroups per CU: 3.8); in the pipeline 0.95 ms (1.04):
+// profiles/r05_tallskinny_blocks_ab.txt.  A form that fed X to the MFMAs straight from registers, never through LDS,
+// measured slower (1.095 vs 1.04 ms) and non-temporal loads of X / stores of Y changed nothing:
+// profiles/r03_tallskinny_ab.txt.
 #include "common.h"
 
 typedef double d2 __attribute__((ext_vector_type(2)));
@@ -31,12 +44,18 @@ struct TsParams {
 
 // RB = 16-row blocks per wave: a workgroup takes 64 RB rows.  With RB = 2 a T stage (re-read from L2 by every workgroup)
 // serves twice as many rows: L2 -> CU traffic per row of X drops from 1.75x to 1.37x of the X bytes at k = 40.
-template <int NT, int RB>
-__global__ __launch_bounds__(TS_THREADS, RB == 2 ? (NT <= 4 ? 3 : 1) : (NT <= 4 ? 4 : 2)) void tallskinny_kernel(const TsParams p) {
+// KF = full 16-column tiles (v_mfma_f64_16x16x4_f64), G = groups of four remainder columns (v_mfma_f64_4x4x4_4b_f64, one
+// instruction per group and 16-row block: its block b is rows 4 b .. 4 b + 3 against the group's four columns).
+template <int KF, int G, int RB>
+__global__ __launch_bounds__(TS_THREADS, RB == 2 ? (KF + (G > 0) <= 4 ? 3 : 1) : (KF + (G > 0) <= 4 ? 4 : 2)) void tallskinny_kernel(const TsParams p) {
+  constexpr int NT = KF + (G > 0);
   constexpr int TS_BM = 64 * RB;
   constexpr int TS_XL = TS_BM * TS_KS / 2 / TS_THREADS;      // d2 loads of X per thread and stage
-  constexpr int KP = 16 * NT;                                 // padded output width
-  constexpr int TL = (TS_KS * KP / 2 + TS_THREADS - 1) / TS_THREADS;  // d2 loads of T per thread and stage
+  constexpr int KP = 16 * NT;                                 // LDS stride of a T stage row (16 mod 32 for odd NT: the
+                                                              // k rows of a B-operand read fall in distinct banks)
+  constexpr int KW = 16 * KF + 4 * G;                         // columns staged: k padded with zeros to the next group
+  constexpr int TL = (TS_KS * KW / 2 + TS_THREADS - 1) / TS_THREADS;  // d2 loads of T per thread and stage
+  constexpr int KF1 = KF > 0 ? KF : 1, G1 = G > 0 ? G : 1;    // array extents (no zero-length arrays)
   __shared__ __attribute__((aligned(16))) double sA[TS_BM * TS_SA];
   __shared__ __attribute__((aligned(16))) double sT[TS_KS * KP];
   const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, l4 = lane >> 4;
@@ -45,11 +64,15 @@ __global__ __launch_bounds__(TS_THREADS, RB == 2 ? (NT <= 4 ? 3 : 1) : (NT <= 4 
   const bool xvec = ((p.ldx & 1) == 0) && ((reinterpret_cast<size_t>(p.X) & 15) == 0);
   const bool tvec = ((p.ldt & 1) == 0) && ((reinterpret_cast<size_t>(p.T) & 15) == 0);
 
-  d4 acc[RB][NT];
+  d4 acc[RB][KF1];
+  double accg[RB][G1];
 #pragma unroll
-  for (int b = 0; b < RB; ++b)
+  for (int b = 0; b < RB; ++b) {
 #pragma unroll
-    for (int j = 0; j < NT; ++j) acc[b][j] = d4{0.0, 0.0, 0.0, 0.0};
+    for (int j = 0; j < KF1; ++j) acc[b][j] = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int g = 0; g < G1; ++g) accg[b][g] = 0.0;
+  }
 
   d2 xr[TS_XL], tr[TL];
   auto fetch = [&](int c0) {  // stage of contraction columns c0 .. c0 + TS_KS - 1 into registers
@@ -71,7 +94,7 @@ __global__ __launch_bounds__(TS_THREADS, RB == 2 ? (NT <= 4 ? 3 : 1) : (NT <= 4 
     }
 #pragma unroll
     for (int i = 0; i < TL; ++i) {
-      const int q = tid + TS_THREADS * i, kk = q / (KP / 2), j = 2 * (q % (KP / 2));
+      const int q = tid + TS_THREADS * i, kk = q / (KW / 2), j = 2 * (q % (KW / 2));
       d2 v{0.0, 0.0};
       if (kk < TS_KS && c0 + kk < p.n) {
         const double* src = p.T + (long)(c0 + kk) * p.ldt + j;
@@ -93,7 +116,7 @@ __global__ __launch_bounds__(TS_THREADS, RB == 2 ? (NT <= 4 ? 3 : 1) : (NT <= 4 
     }
 #pragma unroll
     for (int i = 0; i < TL; ++i) {
-      const int q = tid + TS_THREADS * i, kk = q / (KP / 2), j = 2 * (q % (KP / 2));
+      const int q = tid + TS_THREADS * i, kk = q / (KW / 2), j = 2 * (q % (KW / 2));
       if (kk < TS_KS) *reinterpret_cast<d2*>(&sT[kk * KP + j]) = tr[i];
     }
   };
@@ -101,8 +124,30 @@ __global__ __launch_bounds__(TS_THREADS, RB == 2 ? (NT <= 4 ? 3 : 1) : (NT <= 4 
   fetch(0);
   commit();
   __syncthreads();
+  // Operand addresses, computed once.  The four-block instruction holds A[blk][i][k] in lane i + 4 blk + 16 k, B[blk][k][j]
+  // in lane j + 4 blk + 16 k and D[blk][i][j] in lane j + 4 blk + 16 i (measured: profiles/r05_mfma_f64_blocks.txt), so with
+  // block blk = rows 4 blk .. 4 blk + 3 its A operand is the 16x16x4 one, register for register, and only B is read anew.
   const double* fa = sA + (16 * wid + l15) * TS_SA + l4;  // A operand: row 16 (w + 4 b) + l15, k = 4 k4 + l4
   const double* fb = sT + l4 * KP + l15;                   // B operand: k = 4 k4 + l4, column 16 j + l15
+  const double* fg = sT + l4 * KP + 16 * KF + (lane & 3);  // B operand of a group: k = 4 k4 + l4, column 16 KF + 4 g + (lane & 3)
+  auto multiply = [&]() {  // the stage in LDS times the accumulators
+#pragma unroll
+    for (int k4 = 0; k4 < TS_KS / 4; ++k4) {
+      double bq[KF1], bg[G1];
+#pragma unroll
+      for (int j = 0; j < KF; ++j) bq[j] = fb[4 * k4 * KP + 16 * j];
+#pragma unroll
+      for (int g = 0; g < G; ++g) bg[g] = fg[4 * k4 * KP + 4 * g];
+#pragma unroll
+      for (int b = 0; b < RB; ++b) {
+        const double a = fa[64 * b * TS_SA + 4 * k4];
+#pragma unroll
+        for (int j = 0; j < KF; ++j) acc[b][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bq[j], acc[b][j], 0, 0, 0);
+#pragma unroll
+        for (int g = 0; g < G; ++g) accg[b][g] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, bg[g], accg[b][g], 0, 0, 0);
+      }
+    }
+  };
   int c0 = 0;
   // Fast loop for workgroups whose 64 rows exist and whose stages are whole (n a multiple of 32, 16-byte aligned pairs):
   // the refill addresses are a wave-uniform base, advanced by scalar adds, plus per-thread byte offsets computed once
@@ -119,9 +164,9 @@ __global__ __launch_bounds__(TS_THREADS, RB == 2 ? (NT <= 4 ? 3 : 1) : (NT <= 4 
     bool tuse[TL];
 #pragma unroll
     for (int i = 0; i < TL; ++i) {
-      const int q = tid + TS_THREADS * i, kk = q / (KP / 2), j = 2 * (q % (KP / 2));
+      const int q = tid + TS_THREADS * i, kk = q / (KW / 2), j = 2 * (q % (KW / 2));
       toff[i] = (unsigned)(((long)kk * p.ldt + j) * 8);
-      tuse[i] = j + 1 < p.k;                                                        // padded columns stay zero
+      tuse[i] = kk < TS_KS && j + 1 < p.k;                                          // padded columns stay zero
       tr[i] = d2{0.0, 0.0};
     }
     const long tstage = (long)TS_KS * p.ldt * 8;
@@ -131,18 +176,7 @@ __global__ __launch_bounds__(TS_THREADS, RB == 2 ? (NT <= 4 ? 3 : 1) : (NT <= 4 
 #pragma unroll
       for (int i = 0; i < TL; ++i)
         if (tuse[i]) tr[i] = *reinterpret_cast<const d2*>(gt + toff[i]);
-#pragma unroll
-      for (int k4 = 0; k4 < TS_KS / 4; ++k4) {
-        double bq[NT];
-#pragma unroll
-        for (int j = 0; j < NT; ++j) bq[j] = fb[4 * k4 * KP + 16 * j];
-#pragma unroll
-        for (int b = 0; b < RB; ++b) {
-          const double a = fa[64 * b * TS_SA + 4 * k4];
-#pragma unroll
-          for (int j = 0; j < NT; ++j) acc[b][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bq[j], acc[b][j], 0, 0, 0);
-        }
-      }
+      multiply();
       gx += TS_KS * 8;
       gt += tstage;
       __syncthreads();
@@ -153,32 +187,39 @@ __global__ __launch_bounds__(TS_THREADS, RB == 2 ? (NT <= 4 ? 3 : 1) : (NT <= 4 
   for (; c0 < p.n; c0 += TS_KS) {
     const bool more = c0 + TS_KS < p.n;
     if (more) fetch(c0 + TS_KS);
-#pragma unroll
-    for (int k4 = 0; k4 < TS_KS / 4; ++k4) {
-      double bq[NT];
-#pragma unroll
-      for (int j = 0; j < NT; ++j) bq[j] = fb[4 * k4 * KP + 16 * j];
-#pragma unroll
-      for (int b = 0; b < RB; ++b) {
-        const double a = fa[64 * b * TS_SA + 4 * k4];
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[b][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bq[j], acc[b][j], 0, 0, 0);
-      }
-    }
+    multiply();
     __syncthreads();
     if (more) commit();
     __syncthreads();
   }
 #pragma unroll
-  for (int b = 0; b < RB; ++b)
+  for (int b = 0; b < RB; ++b) {
 #pragma unroll
-    for (int j = 0; j < NT; ++j)
+    for (int j = 0; j < KF; ++j)
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const long row = row0 + 64 * b + 16 * wid + l4 + 4 * c;
         const int col = 16 * j + l15;
         if (row < p.N && col < p.k) p.Y[row * p.ldy + col] = acc[b][j][c];
       }
+#pragma unroll
+    for (int g = 0; g < G; ++g) {  // D[blk][i][j] of the four-block form: blk = (lane >> 2) & 3, i = lane >> 4, j = lane & 3
+      const long row = row0 + 64 * b + 16 * wid + (l15 & 12) + l4;
+      const int col = 16 * KF + 4 * g + (lane & 3);
+      if (row < p.N && col < p.k) p.Y[row * p.ldy + col] = accg[b][g];
+    }
+  }
+}
+
+template <int KF, int G>
+void ts_launch(int rb, unsigned grid, hipStream_t stream, const TsParams& p) {
+  if constexpr (KF + (G > 0) <= 4) {
+    if (rb == 2) {
+      hipLaunchKernelGGL((tallskinny_kernel<KF, G, 2>), dim3(grid), dim3(TS_THREADS), 0, stream, p);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((tallskinny_kernel<KF, G, 1>), dim3(grid), dim3(TS_THREADS), 0, stream, p);
 }
 
 }  // namespace
@@ -200,20 +241,18 @@ int rt_tallskinny(rt_ctx* ctx, const double* X, int64_t ldx, const double* T, in
     }
     RT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   }
-#define TS_LAUNCH(NT_)                                                                                                  \
-  if (rb == 2) hipLaunchKernelGGL((tallskinny_kernel<(NT_ <= 4 ? NT_ : 4), 2>), dim3(grid), dim3(TS_THREADS), 0, ctx->stream, p); \
-  else hipLaunchKernelGGL((tallskinny_kernel<NT_, 1>), dim3(grid), dim3(TS_THREADS), 0, ctx->stream, p)
-  switch (nt) {
-    case 1: TS_LAUNCH(1); break;
-    case 2: TS_LAUNCH(2); break;
-    case 3: TS_LAUNCH(3); break;
-    case 4: TS_LAUNCH(4); break;
-    case 5: TS_LAUNCH(5); break;
-    case 6: TS_LAUNCH(6); break;
-    case 7: TS_LAUNCH(7); break;
-    default: TS_LAUNCH(8); break;
+  // 1 <= k % 16 <= 12: the remainder goes through ceil((k % 16) / 4) four-block instructions; otherwise whole tiles only
+  const int c = (int)(k % 16);
+  const int kf = (c == 0 || c >= 13) ? nt : nt - 1, g = (c == 0 || c >= 13) ? 0 : (c + 3) / 4;
+#define TS_CASE(KF_, G_) case 4 * (KF_) + (G_): ts_launch<KF_, G_>(rb, grid, ctx->stream, p); break;
+#define TS_ROW(KF_) TS_CASE(KF_, 0) TS_CASE(KF_, 1) TS_CASE(KF_, 2) TS_CASE(KF_, 3)
+  switch (4 * kf + g) {
+    TS_CASE(0, 1) TS_CASE(0, 2) TS_CASE(0, 3)
+    TS_ROW(1) TS_ROW(2) TS_ROW(3) TS_ROW(4) TS_ROW(5) TS_ROW(6) TS_ROW(7)
+    default: ts_launch<8, 0>(rb, grid, ctx->stream, p); break;
   }
-#undef TS_LAUNCH
+#undef TS_ROW
+#undef TS_CASE
   RT_HIP_CHECK(ctx, hipGetLastError());
   if (ctx->profile) {
     RT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
