@@ -5,6 +5,7 @@ without a GPU; the .so lands in ``romtime_amd/lib/`` (git-ignored, shipped by gp
 """
 from __future__ import annotations
 
+import glob
 import os
 import subprocess
 import sys
@@ -37,7 +38,8 @@ def _stale(target, deps):
 def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(LIBDIR, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_panel.h"), os.path.join(CSRC, "wave_ops.h"), os.path.join(CSRC, "host_dense.h"), os.path.join(CSRC, "sweep_advance.h"), os.path.join(HERE, "..", "include", "romtime_hip.h")]
+    # every header is a dependency of every object: coarse, but a list kept by hand goes stale (it missed tile_layout.h)
+    headers = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "romtime_hip.h")]
     objs, jobs = [], []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

@@ -120,19 +120,8 @@ int rt_skinny_tn(rt_ctx* ctx, const double* A, int64_t lda, const double* B, int
                  double* Cm, int64_t ldc);
 
 // Newton-Schulz inverse tracking solve for the online sweep (solve.hip); RT_ERR_UNSUPPORTED for r > 80.
-struct rt_newton_rhs {  // b = M_N (c0 u^n + c1 u^{n-1}) + dt Zf^T F_rhs, per system; MN == nullptr: rhs is given
-  const double* MN;    // B x r x r
-  const double* un;    // B x r
-  const double* unm1;  // B x r
-  double c0, c1, dt;
-  const double* Ff;    // B x mf
-  const double* Zf;    // mf x r
-  int mf;
-  long mn_stride = -1;        // doubles between the M_N of consecutive systems (-1: r * r; 0: one M_N for all)
-  const long* ctr = nullptr;  // device step counter: Ff is the table base and the step's rows start at *ctr * ff_stride
-  long ff_stride = 0;         // (graph replay of a sweep: the launch parameters cannot carry the step)
-};
-struct rt_advance;  // sweep_advance.h: the hyper-reduced sweep's end-of-step work, run as the tail of the solver kernels
+struct rt_newton_rhs;  // sweep_step.h: how a step's right-hand side is formed ...
+struct rt_advance;     // ... and how the step is closed, in the solver kernel's tail
 int rt_newton_solve_batched(rt_ctx* ctx, const double* K, double* Xinv, double* rhs, int64_t r, int64_t B,
                             int have_prev, int* info, const rt_newton_rhs* recipe = nullptr,
                             const rt_advance* advance = nullptr);

@@ -21,7 +21,7 @@
 // registers whose entries come out wave-uniform through readlane.  Elementwise steps are evaluated as NumPy evaluates
 // them (no contraction: #pragma below); the BLAS-like sums (mat-vec, dot products, y V) use fused multiply-adds.
 #include "common.h"
-#include "sweep_advance.h"
+#include "sweep_step.h"
 #include "wave_ops.h"
 
 #pragma clang fp contract(off)

@@ -15,7 +15,7 @@
 //   * back substitution runs in the first wave alone (no barriers).
 #include "common.h"
 #include "wave_ops.h"
-#include "sweep_advance.h"
+#include "sweep_step.h"
 #include "tile_layout.h"
 
 typedef double d4 __attribute__((ext_vector_type(4)));
@@ -141,10 +141,7 @@ __device__ __forceinline__ int lu_solve_lds(double* A, int lda, double* b, int r
 
 __global__ __launch_bounds__(SOLVE_THREADS) void dense_solve_kernel(const double* __restrict__ K,
                                                                     double* __restrict__ rhs, int r, int parts,
-                                                                    int* info, const int* only_if, long* counters,
-                                                                    const rt_advance adv) {
-  if (only_if && only_if[blockIdx.x] == 0) return;  // fallback launch: only the systems another solver gave up on
-  if (only_if && threadIdx.x == 0) atomicAdd(reinterpret_cast<unsigned long long*>(&counters[RT_CNT_LU_FALLBACK]), 1ull);
+                                                                    int* info) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int lda = r | 1;  // odd leading dimension: column walks hit distinct banks
   double* A = sm;         // r x lda
@@ -158,10 +155,6 @@ __global__ __launch_bounds__(SOLVE_THREADS) void dense_solve_kernel(const double
   __syncthreads();
   const int sing = lu_solve_lds<SOLVE_THREADS>(A, lda, b, r, parts, rb);
   if (info && tid == 0) info[blockIdx.x] = sing ? RT_WARN_SINGULAR : 0;
-  if (adv.enabled) {  // the hyper-reduced sweep's end of step for this system (its solver kernel left it alone)
-    __syncthreads();  // rb is complete and visible in this workgroup
-    hsweep_advance_rows(adv, blockIdx.x, r, rhs, 1, b, tid, SOLVE_THREADS);
-  }
 }
 
 // K X = B for MANY right-hand sides against one matrix (folding an interpolation matrix PT_U into the expansion of a
@@ -582,16 +575,7 @@ __global__ __launch_bounds__(NS_THREADS) void newton_solve_kernel(const double* 
 
 }  // namespace
 
-
-static int dense_solve_launch(rt_ctx* ctx, double* K, double* rhs, int64_t r, int64_t B, int* info, const int* only_if,
-                              const rt_advance* advance);
-
 extern "C" int rt_dense_solve_batched(rt_ctx* ctx, double* K, double* rhs, int64_t r, int64_t B, int* info) {
-  return dense_solve_launch(ctx, K, rhs, r, B, info, nullptr, nullptr);
-}
-
-static int dense_solve_launch(rt_ctx* ctx, double* K, double* rhs, int64_t r, int64_t B, int* info, const int* only_if,
-                              const rt_advance* advance) {
   if (!ctx) return RT_ERR_ARG;
   RT_ARG_CHECK(ctx, K && rhs && r >= 1 && B >= 1);
   if (r > 128) {
@@ -604,7 +588,7 @@ static int dense_solve_launch(rt_ctx* ctx, double* K, double* rhs, int64_t r, in
   int parts = SOLVE_THREADS / (int)r;  // threads per row
   if (parts > 8) parts = 8;
   hipLaunchKernelGGL(dense_solve_kernel, dim3((unsigned)B), dim3(SOLVE_THREADS), lds, ctx->stream, K, rhs, (int)r,
-                     parts, info, only_if, ctx->dev_counters, advance ? *advance : rt_advance{});
+                     parts, info);
   RT_HIP_CHECK(ctx, hipGetLastError());
   return RT_OK;
 }

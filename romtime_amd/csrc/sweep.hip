@@ -10,7 +10,7 @@
 // The operators are affine in precomputed value vectors on one CSR pattern (the form MDEIM itself
 // produces, and what a closed-form 1-D assembly yields); the state-dependent term is diag(u*) T.
 #include "common.h"
-#include "sweep_advance.h"
+#include "sweep_step.h"
 
 typedef double xd2 __attribute__((ext_vector_type(2)));
 typedef double xd4 __attribute__((ext_vector_type(4)));
@@ -174,35 +174,6 @@ __global__ __launch_bounds__(256) void sweep_values_kernel(const double* __restr
   }
 }
 
-// rhs[b] = M_N (c0 u_n[b] + c1 u_nm1[b]) + dt * sum_f rcoef[b][f] * fN[f]
-__global__ void sweep_rhs_kernel(const double* __restrict__ MN, const double* __restrict__ un,
-                                 const double* __restrict__ unm1, double c0, double c1, double dt,
-                                 const double* __restrict__ rcoef, const double* __restrict__ fN, int F, int r,
-                                 double* __restrict__ rhs) {
-  extern __shared__ double su[];
-  const int b = blockIdx.x, t = threadIdx.x;
-  if (t < r) su[t] = c0 * un[(long)b * r + t] + c1 * unm1[(long)b * r + t];
-  __syncthreads();
-  if (t < r) {
-    double acc = 0.0;
-    for (int j = 0; j < r; ++j) acc = fma(MN[(long)t * r + j], su[j], acc);
-    double f = 0.0;
-    for (int q = 0; q < F; ++q) f = fma(rcoef[(long)b * F + q], fN[(long)q * r + t], f);
-    rhs[(long)b * r + t] = fma(dt, f, acc);
-  }
-}
-
-__global__ void sweep_store_kernel(const double* __restrict__ x, double* __restrict__ un, double* __restrict__ unm1,
-                                   double* __restrict__ out, long step, long nt, int r, int keep_prev) {
-  const int b = blockIdx.x, t = threadIdx.x;
-  if (t < r) {
-    const double v = x[(long)b * r + t];
-    if (keep_prev) unm1[(long)b * r + t] = un[(long)b * r + t];
-    un[(long)b * r + t] = v;
-    out[((long)b * nt + step) * r + t] = v;
-  }
-}
-
 // ---- hyper-reduced sweep -----------------------------------------------------------------------------------
 // G[b] = [ bdf F_mass | dt F_lin | dt S (W u* + C) ]  (one row of interpolation coefficients per parameter point)
 // and G[B + b] = [ F_mass | 0 | 0 ], so that ONE skinny GEMM with Z yields K_N (rows 0..B-1) and M_N (rows B..2B-1)
@@ -215,23 +186,78 @@ __global__ void hsweep_advance_kernel(const double* __restrict__ x, int do_store
 
 __global__ void hsweep_count_kernel(long* ctr) { *ctr += 1; }
 
-// rhs[b] = M_N[b] (c0 u_n[b] + c1 u_nm1[b]) + dt Zf^T F_rhs[b]
-__global__ void hsweep_rhs_kernel(const double* __restrict__ MN, const double* __restrict__ un,
-                                  const double* __restrict__ unm1, double c0, double c1, double dt,
-                                  const double* __restrict__ Ff, const double* __restrict__ Zf, int mf, int r,
-                                  double* __restrict__ rhs) {
+// rhs[b] = M_N[b] (c0 u_n[b] + c1 u_nm1[b]) + dt Zf^T Ff[b]: the recipe the solver kernels evaluate in their own
+// prologue, as a kernel for the r > 80 route; one thread per row, every sum in sequence
+__global__ void step_rhs_kernel(const rt_newton_rhs rq, int r, double* __restrict__ rhs) {
   extern __shared__ double su[];
   const int b = blockIdx.x, t = threadIdx.x;
-  if (t < r) su[t] = c0 * un[(long)b * r + t] + c1 * unm1[(long)b * r + t];
+  if (t < r) su[t] = rq.c0 * rq.un[(long)b * r + t] + rq.c1 * rq.unm1[(long)b * r + t];
   __syncthreads();
   if (t < r) {
-    const double* M = MN + (long)b * r * r + (long)t * r;
+    const double* M = rq.MN + (long)b * (rq.mn_stride < 0 ? (long)r * r : rq.mn_stride) + (long)t * r;
+    const double* Ff = (rq.ctr ? rq.Ff + *rq.ctr * rq.ff_stride : rq.Ff) + (long)b * rq.mf;
     double acc = 0.0;
     for (int j = 0; j < r; ++j) acc = fma(M[j], su[j], acc);
     double f = 0.0;
-    for (int e = 0; e < mf; ++e) f = fma(Ff[(long)b * mf + e], Zf[(long)e * r + t], f);
-    rhs[(long)b * r + t] = fma(dt, f, acc);
+    for (int e = 0; e < rq.mf; ++e) f = fma(Ff[e], rq.Zf[(long)e * r + t], f);
+    rhs[(long)b * r + t] = fma(rq.dt, f, acc);
   }
+}
+
+// The reduced solver's buffers, the same in both sweeps
+struct StepWork {
+  double* KN;     // kn_mats x r x r: the step's matrices (the hyper-reduced sweep stacks its M_N behind them)
+  double* rhs;    // B x r: right-hand sides, then solutions
+  double* un;     // B x r
+  double* unm1;   // B x r
+  double* Xinv;   // B x r x r: K_N^-1 of the previous step, per parameter point
+  int* info;      // B
+  double* gwork;  // GMRES mode: Krylov bases that do not fit the LDS
+};
+
+// Takes the composite arena ONCE, for the solver's buffers and `extra` bytes of the sweep's own (*extra_base, 256-B
+// aligned), and zeroes the state and the sweep's counters on the ctx stream.
+int step_work_get(rt_ctx* ctx, long r, long B, long kn_mats, size_t extra, StepWork* w, char** extra_base) {
+  size_t off = 0;
+  auto take = [&off](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+  const bool gmres = ctx->reduced_solver == RT_SOLVER_GMRES;
+  const size_t oKN = take(sizeof(double) * kn_mats * r * r), oRhs = take(sizeof(double) * B * r),
+               oUn = take(sizeof(double) * B * r), oUm = take(sizeof(double) * B * r),
+               oXi = take(sizeof(double) * B * r * r), oInfo = take(sizeof(int) * B),
+               oGw = take(gmres ? rt_gmres_work_bytes(r, B, &ctx->gmres_opts) : 0);
+  void* base = nullptr;
+  RT_TRY(rt_scratch2(ctx, off + extra, &base));
+  char* b8 = static_cast<char*>(base);
+  w->KN = reinterpret_cast<double*>(b8 + oKN);
+  w->rhs = reinterpret_cast<double*>(b8 + oRhs);
+  w->un = reinterpret_cast<double*>(b8 + oUn);
+  w->unm1 = reinterpret_cast<double*>(b8 + oUm);
+  w->Xinv = reinterpret_cast<double*>(b8 + oXi);
+  w->info = reinterpret_cast<int*>(b8 + oInfo);
+  w->gwork = reinterpret_cast<double*>(b8 + oGw);
+  *extra_base = b8 + off;
+  RT_HIP_CHECK(ctx, hipMemsetAsync(w->un, 0, sizeof(double) * B * r, ctx->stream));
+  RT_HIP_CHECK(ctx, hipMemsetAsync(w->unm1, 0, sizeof(double) * B * r, ctx->stream));
+  RT_HIP_CHECK(ctx, hipMemsetAsync(ctx->dev_counters + RT_CNT_NS_ITER, 0, sizeof(long) * 6, ctx->stream));  // stats + GMRES counters
+  return RT_OK;
+}
+
+// Solves the B systems K_b x_b = rhs(rq) with the ctx's reduced solver and closes the step as `adv` says.  One launch:
+// the solver kernel forms the right-hand side, the tracked solve falls back to its LU by itself where the tracking
+// fails, and the kernel's tail closes the step.  r > 80, where the tracked solve's three matrices do not fit the LDS:
+// three launches - right-hand side, plain pivoted LU, step close.
+int sweep_step_solve(rt_ctx* ctx, const StepWork& w, long r, long B, int have_prev, const rt_newton_rhs& rq,
+                     const rt_advance& adv) {
+  const int rc = ctx->reduced_solver == RT_SOLVER_GMRES
+                     ? rt_gmres_launch(ctx, w.KN, nullptr, w.rhs, r, B, &ctx->gmres_opts, nullptr, nullptr, w.gwork, &rq, &adv, true)
+                     : rt_newton_solve_batched(ctx, w.KN, w.Xinv, w.rhs, r, B, have_prev, w.info, &rq, &adv);
+  if (rc != RT_ERR_UNSUPPORTED) return rc;
+  hipLaunchKernelGGL(step_rhs_kernel, dim3((unsigned)B), dim3(128), sizeof(double) * r, ctx->stream, rq, (int)r, w.rhs);
+  RT_HIP_CHECK(ctx, hipGetLastError());
+  RT_TRY(rt_dense_solve_batched(ctx, w.KN, w.rhs, r, B, w.info));
+  hipLaunchKernelGGL(hsweep_advance_kernel, dim3((unsigned)B), dim3(256), sizeof(double) * r, ctx->stream, w.rhs, 1, (int)r, adv);
+  RT_HIP_CHECK(ctx, hipGetLastError());
+  return RT_OK;
 }
 
 }  // namespace
@@ -245,41 +271,26 @@ extern "C" int rt_rom_bdf_sweep(rt_ctx* ctx, const rt_sweep_desc* d, double* uN_
   const long N = d->N, nnz = d->nnz, r = d->r, B = d->n_mu, nt = d->nt;
   const int Q = (int)d->n_terms, F = (int)d->n_rhs;
   hipStream_t st = ctx->stream;
-  const bool gmres = ctx->reduced_solver == RT_SOLVER_GMRES;
 
-  // workspace (composite arena)
+  // workspace (composite arena): the solver's buffers, then this sweep's own
   size_t off = 0;
   auto take = [&off](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
   const size_t oRow = take(sizeof(int) * nnz), oMN = take(sizeof(double) * r * r), oFN = take(sizeof(double) * (F ? F : 1) * r),
-               oKN = take(sizeof(double) * B * r * r), oRhs = take(sizeof(double) * B * r), oUn = take(sizeof(double) * B * r),
-               oUm = take(sizeof(double) * B * r), oUh = take(sizeof(double) * B * N), oUp = take(sizeof(double) * B * N),
-               oXT = take(sizeof(double) * r * B), oInfo = take(sizeof(int) * B),
-               oKv = take(sizeof(double) * B * nnz), oTab = take(rt_project_stage_table_bytes(N)),
-               oXi = take(sizeof(double) * B * r * r),
-               oGw = take(gmres ? rt_gmres_work_bytes(r, B, &ctx->gmres_opts) : 0);
-  void* base = nullptr;
-  int rc = rt_scratch2(ctx, off, &base);
+               oUh = take(sizeof(double) * B * N), oUp = take(sizeof(double) * B * N), oXT = take(sizeof(double) * r * B),
+               oKv = take(sizeof(double) * B * nnz), oTab = take(rt_project_stage_table_bytes(N));
+  StepWork w;
+  char* b8 = nullptr;
+  int rc = step_work_get(ctx, r, B, B, off, &w, &b8);
   if (rc != RT_OK) return rc;
-  char* b8 = static_cast<char*>(base);
   int* row_of = reinterpret_cast<int*>(b8 + oRow);
   double* MN = reinterpret_cast<double*>(b8 + oMN);
   double* fN = reinterpret_cast<double*>(b8 + oFN);
-  double* KN = reinterpret_cast<double*>(b8 + oKN);
-  double* rhs = reinterpret_cast<double*>(b8 + oRhs);
-  double* un = reinterpret_cast<double*>(b8 + oUn);
-  double* unm1 = reinterpret_cast<double*>(b8 + oUm);
   double* uh = reinterpret_cast<double*>(b8 + oUh);
   double* uhp = reinterpret_cast<double*>(b8 + oUp);
   double* xT = reinterpret_cast<double*>(b8 + oXT);
-  int* info = reinterpret_cast<int*>(b8 + oInfo);
   double* kval = reinterpret_cast<double*>(b8 + oKv);
-  double* Xinv = reinterpret_cast<double*>(b8 + oXi);  // K_N^-1 of the previous step, per parameter point
   void* stage_table = b8 + oTab;  // per-pattern stage records of the fused projection, built once per sweep
-  double* gwork = reinterpret_cast<double*>(b8 + oGw);  // GMRES mode: Krylov bases that do not fit the LDS
 
-  RT_HIP_CHECK(ctx, hipMemsetAsync(un, 0, sizeof(double) * B * r, st));
-  RT_HIP_CHECK(ctx, hipMemsetAsync(unm1, 0, sizeof(double) * B * r, st));
-  RT_HIP_CHECK(ctx, hipMemsetAsync(ctx->dev_counters + RT_CNT_NS_ITER, 0, sizeof(long) * 6, st));  // stats + GMRES counters
   RT_HIP_CHECK(ctx, hipMemsetAsync(uh, 0, sizeof(double) * B * N, st));
   RT_HIP_CHECK(ctx, hipMemsetAsync(uhp, 0, sizeof(double) * B * N, st));
   hipLaunchKernelGGL(sweep_rows_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st,
@@ -310,31 +321,18 @@ extern "C" int rt_rom_bdf_sweep(rt_ctx* ctx, const rt_sweep_desc* d, double* uN_
                          d->mass_values, d->term_values, Q, d->term_coef + step * B * Q, d->tril_values, row_of, uh, uhp,
                          d->bdf2 ? 1 : 0, nnz, N, (int)B, second ? 1.5 : 1.0, d->dt, kval);
     RT_HIP_CHECK(ctx, hipGetLastError());
-    rc = rt_project_fused(ctx, d->indptr, d->indices, kval, 1, nnz, B, N, d->V, r, r, KN, stage_table, banded);
+    rc = rt_project_fused(ctx, d->indptr, d->indices, kval, 1, nnz, B, N, d->V, r, r, w.KN, stage_table, banded);
     if (rc != RT_OK) return rc;
     const double c0 = d->bdf2 ? 2.0 : 1.0, c1 = d->bdf2 ? -0.5 : 0.0;  // u^{n-1} = 0 at step 0 reproduces BDF1
     // reference: step 0 of a BDF2 run uses M_N (2 u^0 - u^{-1}/2) with both zero (rom.py:451-458,921-924)
-    // consecutive K_N differ by O(dt): refresh the tracked inverse on the matrix cores; the solve kernel forms the
-    // right-hand side, falls back to LU by itself where the tracking fails, and closes the step (u^n, u^{n-1},
-    // trajectory, u^n transposed for the lift) - one launch where there were four
-    rt_newton_rhs rq{MN, un, unm1, c0, c1, d->dt, F ? d->rhs_coef + step * B * F : nullptr, fN, F};
+    // consecutive K_N differ by O(dt): the tracked solve refreshes the carried inverse on the matrix cores.  The step
+    // closes with u^n, u^{n-1}, the trajectory row and u^n transposed for the lift.
+    rt_newton_rhs rq{MN, w.un, w.unm1, c0, c1, d->dt, F ? d->rhs_coef + step * B * F : nullptr, fN, F};
     rq.mn_stride = 0;
     rt_advance close{};
-    close.un = un; close.unm1 = unm1; close.out = uN_out; close.step_done = step; close.nt = nt;
+    close.un = w.un; close.unm1 = w.unm1; close.out = uN_out; close.step_done = step; close.nt = nt;
     close.keep_prev = d->bdf2 ? 1 : 0; close.do_coef = 0; close.xT = xT; close.B = (int)B; close.enabled = 1;
-    rc = gmres ? rt_gmres_launch(ctx, KN, nullptr, rhs, r, B, &ctx->gmres_opts, nullptr, nullptr, gwork, &rq, &close, true)
-               : rt_newton_solve_batched(ctx, KN, Xinv, rhs, r, B, step > 0 ? 1 : 0, info, &rq, &close);
-    if (rc == RT_ERR_UNSUPPORTED) {  // r > 80: the LDS-resident iteration does not fit
-      hipLaunchKernelGGL(sweep_rhs_kernel, dim3((unsigned)B), dim3(128), sizeof(double) * r, st, MN, un, unm1, c0, c1,
-                         d->dt, F ? d->rhs_coef + step * B * F : nullptr, fN, F, (int)r, rhs);
-      RT_HIP_CHECK(ctx, hipGetLastError());
-      rc = rt_dense_solve_batched(ctx, KN, rhs, r, B, info);
-      if (rc != RT_OK) return rc;
-      hipLaunchKernelGGL(sweep_store_kernel, dim3((unsigned)B), dim3(128), 0, st, rhs, un, unm1, uN_out, step, nt, (int)r,
-                         d->bdf2 ? 1 : 0);
-      RT_HIP_CHECK(ctx, hipGetLastError());
-      rc = rt_transpose(ctx, un, B, r, r, xT, B);
-    }
+    rc = sweep_step_solve(ctx, w, r, B, step > 0 ? 1 : 0, rq, close);
     if (rc != RT_OK) return rc;
     // u_h <- V u_N for every mu, stored [mu][N]; the previous u_h becomes u_h^{n-1}
     double* tmp = uhp; uhp = uh; uh = tmp;
@@ -360,36 +358,23 @@ extern "C" int rt_hrom_bdf_sweep(rt_ctx* ctx, const rt_hsweep_desc* d, double* u
   const long M = mm + ml + mn, rr = r * r;
   hipStream_t st = ctx->stream;
   const bool gmres = ctx->reduced_solver == RT_SOLVER_GMRES;
-  size_t off = 0;
-  auto take = [&off](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-  const size_t oG = take(sizeof(double) * 2 * B * M), oKN = take(sizeof(double) * 2 * B * rr),
-               oRhs = take(sizeof(double) * B * r), oUn = take(sizeof(double) * B * r), oUm = take(sizeof(double) * B * r),
-               oXi = take(sizeof(double) * B * rr), oInfo = take(sizeof(int) * B), oCtr = take(sizeof(long)),
-               oGw = take(gmres ? rt_gmres_work_bytes(r, B, &ctx->gmres_opts) : 0);
-  void* base = nullptr;
-  int rc = rt_scratch2(ctx, off, &base);
+  // the solver's buffers (K_N and M_N of all parameter points stacked: one product yields both), then G and the counter
+  const size_t g_bytes = (sizeof(double) * 2 * B * M + 255) / 256 * 256;
+  StepWork w;
+  char* b8 = nullptr;
+  int rc = step_work_get(ctx, r, B, 2 * B, g_bytes + sizeof(long), &w, &b8);
   if (rc != RT_OK) return rc;
-  char* b8 = static_cast<char*>(base);
-  double* G = reinterpret_cast<double*>(b8 + oG);
-  double* KN = reinterpret_cast<double*>(b8 + oKN);
-  double* MN = KN + B * rr;  // second half of the stacked product
-  double* rhs = reinterpret_cast<double*>(b8 + oRhs);
-  double* un = reinterpret_cast<double*>(b8 + oUn);
-  double* unm1 = reinterpret_cast<double*>(b8 + oUm);
-  double* Xinv = reinterpret_cast<double*>(b8 + oXi);
-  int* info = reinterpret_cast<int*>(b8 + oInfo);
-  long* ctr = reinterpret_cast<long*>(b8 + oCtr);
-  double* gwork = reinterpret_cast<double*>(b8 + oGw);
-  RT_HIP_CHECK(ctx, hipMemsetAsync(un, 0, sizeof(double) * B * r, st));
-  RT_HIP_CHECK(ctx, hipMemsetAsync(unm1, 0, sizeof(double) * B * r, st));
-  RT_HIP_CHECK(ctx, hipMemsetAsync(ctx->dev_counters + RT_CNT_NS_ITER, 0, sizeof(long) * 6, st));  // stats + GMRES counters
+  double* G = reinterpret_cast<double*>(b8);
+  long* ctr = reinterpret_cast<long*>(b8 + g_bytes);
+  double* const KN = w.KN;
+  double* const MN = KN + B * rr;  // second half of the stacked product
 
   // the end-of-step work for closing step next-1 (if any) and preparing the rows of step `next`
   auto advance_args = [&](long next) {
     const bool has_next = next < nt;
     const long s2 = has_next ? next : 0;
     rt_advance a{};
-    a.un = un; a.unm1 = unm1; a.out = uN_out; a.step_done = next - 1; a.nt = nt;
+    a.un = w.un; a.unm1 = w.unm1; a.out = uN_out; a.step_done = next - 1; a.nt = nt;
     a.keep_prev = d->bdf2 ? 1 : 0; a.do_coef = has_next ? 1 : 0;
     a.Fm = d->F_mass + s2 * B * mm; a.Fl = ml ? d->F_lin + s2 * B * ml : nullptr; a.W = d->W;
     a.Cn = d->C_nl ? d->C_nl + s2 * B * mn : nullptr; a.Sn = d->S_nl ? d->S_nl + s2 * B : nullptr;
@@ -397,13 +382,17 @@ extern "C" int rt_hrom_bdf_sweep(rt_ctx* ctx, const rt_hsweep_desc* d, double* u
     a.bdf = (d->bdf2 && next > 0) ? 1.5 : 1.0; a.dt = d->dt; a.G = G; a.ctr = nullptr; a.B = (int)B; a.enabled = 1;
     return a;
   };
-  auto advance = [&](long next, int do_store) {
-    hipLaunchKernelGGL(hsweep_advance_kernel, dim3((unsigned)B), dim3(256), sizeof(double) * r, st, rhs, do_store, (int)r,
-                       advance_args(next));
-  };
-  advance(0, 0);
+  hipLaunchKernelGGL(hsweep_advance_kernel, dim3((unsigned)B), dim3(256), sizeof(double) * r, st, w.rhs, 0, (int)r,
+                     advance_args(0));   // the rows of step 0: nothing to close yet
   RT_HIP_CHECK(ctx, hipGetLastError());
   const double c0 = d->bdf2 ? 2.0 : 1.0, c1 = d->bdf2 ? -0.5 : 0.0;
+  // One step: [K_N; M_N][b][ij] = sum_e G[b][e] Z[e][ij] (2 B rows), then the solve, which forms the right-hand side
+  // and closes the step (state, trajectory, next rows of G) - two launches for r <= 80
+  auto step_body = [&](const rt_newton_rhs& rq, const rt_advance& adv, int have_prev) {
+    int rc2 = rt_expansion_gemm(ctx, G, M, d->Z, rr, KN, rr, 2 * B, M, rr);
+    if (rc2 == RT_ERR_UNSUPPORTED) rc2 = rt_gemm_strided(ctx, G, 1, M, d->Z, rr, 1, M, 2 * B, rr, KN, rr, 1, false, false);
+    return rc2 != RT_OK ? rc2 : sweep_step_solve(ctx, w, r, B, have_prev, rq, adv);
+  };
   // Steps 1 .. nt-1 are the same two launches (expansion GEMM, tracked solve with the end of the step in its tail) with
   // only table offsets moving.  With rt_ctx_set_option(ctx, "sweep_graph", 1) they are captured ONCE as a hipGraph whose
   // kernels take the step from a device counter, and replayed; step 0 runs eagerly (first BDF step, inverse tracking
@@ -430,15 +419,13 @@ extern "C" int rt_hrom_bdf_sweep(rt_ctx* ctx, const rt_hsweep_desc* d, double* u
       ctx->stream = gs;
       st = gs;
       RT_HIP_CHECK(ctx, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-      rc = rt_expansion_gemm(ctx, G, M, d->Z, rr, KN, rr, 2 * B, M, rr);
-      if (rc == RT_ERR_UNSUPPORTED) rc = rt_gemm_strided(ctx, G, 1, M, d->Z, rr, 1, M, 2 * B, rr, KN, rr, 1, false, false);
-      rt_newton_rhs rq{MN, un, unm1, c0, c1, d->dt, mf ? d->F_rhs : nullptr, d->Zf, (int)mf};
+      rt_newton_rhs rq{MN, w.un, w.unm1, c0, c1, d->dt, mf ? d->F_rhs : nullptr, d->Zf, (int)mf};
       rq.ctr = ctr;
       rq.ff_stride = B * mf;
       rt_advance ga = advance_args(1);   // table bases + device counter: the replayed launches cannot carry the step
       ga.Fm = d->F_mass; ga.Fl = ml ? d->F_lin : nullptr; ga.Cn = d->C_nl; ga.Sn = d->S_nl;
       ga.bdf = d->bdf2 ? 1.5 : 1.0; ga.do_coef = 1; ga.ctr = ctr;
-      if (rc == RT_OK) rc = rt_newton_solve_batched(ctx, KN, Xinv, rhs, r, B, 1, info, &rq, &ga);
+      rc = step_body(rq, ga, 1);
       hipLaunchKernelGGL(hsweep_count_kernel, dim3(1), dim3(1), 0, st, ctr);
       const hipError_t cap = hipStreamEndCapture(st, &graph);
       if (rc != RT_OK || cap != hipSuccess || graph == nullptr) {
@@ -462,27 +449,9 @@ extern "C" int rt_hrom_bdf_sweep(rt_ctx* ctx, const rt_hsweep_desc* d, double* u
       RT_HIP_CHECK(ctx, le);
       break;
     }
-    // [K_N; M_N][b][ij] = sum_e G[b][e] Z[e][ij]  (2 B rows)
-    rc = rt_expansion_gemm(ctx, G, M, d->Z, rr, KN, rr, 2 * B, M, rr);
-    if (rc == RT_ERR_UNSUPPORTED) rc = rt_gemm_strided(ctx, G, 1, M, d->Z, rr, 1, M, 2 * B, rr, KN, rr, 1, false, false);
+    const rt_newton_rhs rq{MN, w.un, w.unm1, c0, c1, d->dt, mf ? d->F_rhs + step * B * mf : nullptr, d->Zf, (int)mf};
+    rc = step_body(rq, advance_args(step + 1), step > 0 ? 1 : 0);
     if (rc != RT_OK) return rc;
-    rt_newton_rhs rq{MN, un, unm1, c0, c1, d->dt, mf ? d->F_rhs + step * B * mf : nullptr, d->Zf, (int)mf};
-    // two launches per step: the expansion GEMM and the solve, which forms the right-hand side, falls back to a
-    // pivoted LU by itself where the tracked inverse fails, and closes the step (state, trajectory, next rows of G)
-    const rt_advance adv = advance_args(step + 1);
-    rc = gmres ? rt_gmres_launch(ctx, KN, nullptr, rhs, r, B, &ctx->gmres_opts, nullptr, nullptr, gwork, &rq, &adv, true)
-               : rt_newton_solve_batched(ctx, KN, Xinv, rhs, r, B, step > 0 ? 1 : 0, info, &rq, &adv);
-    if (rc == RT_OK) {
-      RT_HIP_CHECK(ctx, hipGetLastError());
-      continue;
-    } else if (rc == RT_ERR_UNSUPPORTED) {  // r > 80: right-hand side by its own kernel, then the LU
-      hipLaunchKernelGGL(hsweep_rhs_kernel, dim3((unsigned)B), dim3(128), sizeof(double) * r, st, MN, un, unm1, c0, c1,
-                         d->dt, mf ? d->F_rhs + step * B * mf : nullptr, d->Zf, (int)mf, (int)r, rhs);
-      rc = rt_dense_solve_batched(ctx, KN, rhs, r, B, info);
-    }
-    if (rc != RT_OK) return rc;
-    advance(step + 1, 1);
-    RT_HIP_CHECK(ctx, hipGetLastError());
   }
   return RT_OK;
 }

@@ -1,8 +1,25 @@
-// Closing a step of the hyper-reduced sweep and preparing the coefficient rows of the next one, for ONE parameter
-// point: what hsweep_advance_kernel does per workgroup.  A header because the same code runs as the tail of the two
-// solver kernels (solve.hip) - the step is then gemm + solve (+ the LU kernel for the systems the inverse tracking
-// gave up on) instead of four launches, and the host of the pool's boxes sustains only about one launch per 20 us.
+// One step of an online sweep, described by value for the kernels that run it: how the right-hand side is formed
+// (rt_newton_rhs) and how the step is closed once the systems are solved (rt_advance: state, previous state,
+// trajectory row, the coefficient rows of the next step, the state transposed for the direct sweep's lift).
+// hsweep_advance_rows closes the step for ONE parameter point.  It runs as the tail of newton_solve_kernel (solve.hip)
+// and of gmres_kernel (gmres.hip), so that a step is expansion + solve instead of four launches (the host of the pool's
+// boxes sustains only about one launch per 20 us), and in the stand-alone hsweep_advance_kernel (sweep.hip) before the
+// first step and after the plain LU of the r > 80 route.
 #pragma once
+
+// b = M_N (c0 u^n + c1 u^{n-1}) + dt Zf^T F_rhs, per system; MN == nullptr: rhs is given
+struct rt_newton_rhs {
+  const double* MN;    // B x r x r
+  const double* un;    // B x r
+  const double* unm1;  // B x r
+  double c0, c1, dt;
+  const double* Ff;    // B x mf
+  const double* Zf;    // mf x r
+  int mf;
+  long mn_stride = -1;        // doubles between the M_N of consecutive systems (-1: r * r; 0: one M_N for all)
+  const long* ctr = nullptr;  // device step counter: Ff is the table base and the step's rows start at *ctr * ff_stride
+  long ff_stride = 0;         // (graph replay of a sweep: the launch parameters cannot carry the step)
+};
 
 struct rt_advance {
   double* un;            // B x r   u^n            (updated)
