@@ -5,9 +5,9 @@ import torch
 from scipy.sparse import csr_matrix
 
 from oracle import romtime_oracle as oracle
+from tests.solve_cases import EPS, F_BATCHED, error_ratios, reference_solve, synthetic_hrom_terms
 
 pytestmark = pytest.mark.gpu
-EPS = 2.2e-16
 
 
 @pytest.fixture(scope="module")
@@ -356,10 +356,15 @@ def test_dense_solve(ops, r, B):
     K = rng.standard_normal((B, r, r)) + np.eye(r) * 0.1
     b = rng.standard_normal((B, r))
     x, info = ops.dense_solve(ops.to_device(K), ops.to_device(b))
-    ref = np.linalg.solve(K, b[..., None])[..., 0]
-    res = np.abs(np.einsum("bij,bj->bi", K, x.cpu().numpy()) - b).max()
+    x = x.cpu().numpy()
+    res = np.abs(np.einsum("bij,bj->bi", K, x) - b).max()
     assert res < 1e-10
-    np.testing.assert_allclose(x.cpu().numpy(), ref, rtol=1e-8, atol=1e-10)
+    # forward and backward error against the 50-digit solution, as a ratio to LAPACK's on the same system: the bar of
+    # tests/test_reduced_solves_gpu.py (solve_cases.F_BATCHED, ten times the worst ratio measured there)
+    ratios = [error_ratios(K[i], b[i], x[i], reference_solve(K[i], b[i])) for i in range(B)]
+    fwd, bwd = (max(c) for c in zip(*ratios))
+    print(f"ratio to LAPACK batched r={r}, worst of {B}: forward {fwd:.3g} backward {bwd:.3g}")
+    assert fwd <= F_BATCHED[0] and bwd <= F_BATCHED[1], ratios
     assert int(info.abs().sum().item()) == 0
 
 
@@ -560,25 +565,8 @@ def test_hyper_reduced_sweep_synthetic_and_singular_system(ops):
 
     rng = np.random.RandomState(3)
     r, nt, n_mu, dt = 11, 9, 3, 1e-2
-    spd = lambda: (lambda a: a @ a.T + r * np.eye(r))(rng.standard_normal((r, r)))
-
-    def matrix_term(m, base, wobble):
-        # operator(mu, t) = (1 + wobble(mu, t)) * base + small random modes, as an m-mode interpolation expansion
-        cols = np.concatenate([base.reshape(-1, 1), 0.05 * rng.standard_normal((r * r, m - 1))], axis=1)
-        PT_U, _ = np.linalg.qr(rng.standard_normal((m, m)))
-        theta = np.concatenate([1.0 + wobble[..., None], 0.1 * rng.standard_normal((nt, n_mu, m - 1))], axis=-1)
-        return dict(PT_U=PT_U, basis_rom=cols, F=theta @ PT_U.T)
-
-    wob = lambda: 0.1 * rng.standard_normal((nt, n_mu))
     for bdf2 in (True, False):
-        mass = matrix_term(4, spd(), 0.0 * wob())
-        lin = [matrix_term(3, spd(), wob()), matrix_term(5, rng.standard_normal((r, r)), wob())]
-        m_nl = 6
-        PTn, _ = np.linalg.qr(rng.standard_normal((m_nl, m_nl)))
-        nl = dict(PT_U=PTn, basis_rom=0.3 * rng.standard_normal((r * r, m_nl)), W=0.2 * rng.standard_normal((m_nl, r)),
-                  C=0.1 * rng.standard_normal((nt, n_mu, m_nl)), S=1.0 + 0.1 * rng.standard_normal((nt, n_mu)))
-        PTf, _ = np.linalg.qr(rng.standard_normal((4, 4)))
-        rhs = [dict(PT_U=PTf, basis_rom=rng.standard_normal((r, 4)), F=rng.standard_normal((nt, n_mu, 4)))]
+        mass, lin, nl, rhs = synthetic_hrom_terms(rng, r, nt, n_mu, 4, [(3, "spd"), (5, "general")], 6, 4, wobble_tables=True)
         uN = hrom_bdf_sweep(mass, lin, nl, rhs, dt, bdf2=bdf2).cpu().numpy()
         for b in range(n_mu):
             ref = oracle.hrom_solve(mass, lin, nl, rhs, b, r, nt, dt, bdf2)
@@ -612,20 +600,7 @@ def test_sweeps_beyond_the_tracked_solve(ops, bdf2):
 
     rng = np.random.RandomState(7)
     r, nt, n_mu, dt = 96, 5, 2, 1e-2
-    spd = lambda: (lambda a: a @ a.T + r * np.eye(r))(rng.standard_normal((r, r)))
-
-    def matrix_term(m, base):
-        cols = np.concatenate([base.reshape(-1, 1), 0.05 * rng.standard_normal((r * r, m - 1))], axis=1)
-        PT_U, _ = np.linalg.qr(rng.standard_normal((m, m)))
-        theta = np.concatenate([1.0 + 0.1 * rng.standard_normal((nt, n_mu, 1)), 0.1 * rng.standard_normal((nt, n_mu, m - 1))], axis=-1)
-        return dict(PT_U=PT_U, basis_rom=cols, F=theta @ PT_U.T)
-
-    mass, lin = matrix_term(3, spd()), [matrix_term(4, spd())]
-    PTn, _ = np.linalg.qr(rng.standard_normal((5, 5)))
-    nl = dict(PT_U=PTn, basis_rom=0.3 * rng.standard_normal((r * r, 5)), W=0.2 * rng.standard_normal((5, r)),
-              C=0.1 * rng.standard_normal((nt, n_mu, 5)), S=1.0 + 0.1 * rng.standard_normal((nt, n_mu)))
-    PTf, _ = np.linalg.qr(rng.standard_normal((3, 3)))
-    rhs = [dict(PT_U=PTf, basis_rom=rng.standard_normal((r, 3)), F=rng.standard_normal((nt, n_mu, 3)))]
+    mass, lin, nl, rhs = synthetic_hrom_terms(rng, r, nt, n_mu, 3, [(4, "spd")], 5, 3)
     uN = hrom_bdf_sweep(mass, lin, nl, rhs, dt, bdf2=bdf2).cpu().numpy()
     for b in range(n_mu):
         ref = oracle.hrom_solve(mass, lin, nl, rhs, b, r, nt, dt, bdf2)
