@@ -6,7 +6,7 @@
 //   n < 3) -> sigma, energy, truncation rank with the reference's precedence tol > num > 1e-7 (pod.py:46-57) ->
 //     shallow spectrum (sigma_r >= 1e-2 sigma_1): k eigenvectors (+ a k x k Rayleigh-Ritz step when kept eigenvalues
 //       are closer than 1e-4 lambda_1), Q = X D^-1 W S^-1;
-//     deep spectrum: deflated levels - accept the modes within 1e-2 of the current largest singular value, project them
+//     deep spectrum: deflated levels - accept the modes within 0.08 of the current largest singular value, project them
 //       out of a working copy of the snapshots twice, Gram + eigensolve again (DESIGN.md "POD accuracy").
 // The small dense steps on the host (truncation rule, k x k generalised eigenproblem of the Rayleigh-Ritz step) are
 // O(k^3) scalar work on kilobytes; everything of size N_h stays on the device.
@@ -21,7 +21,8 @@ namespace {
 
 constexpr double TWO_PASS_RATIO = 1e-2;   // one Gram pass resolves vectors to eps (sigma_1/sigma_i)^2
 constexpr double RR_GAP = 1e-4;           // eigenvalue gap (relative to lambda_1) below which inverse iteration is not trusted
-constexpr int MAX_LEVELS = 12;
+constexpr double LEVEL_RATIO = 0.08;      // a deflated level accepts the modes within this ratio of its largest (pod.py)
+constexpr int MAX_LEVELS = 16;
 
 // Zs[i][j] = Z[i][j] * rowscale[i] * colscale[j]   (n x k, row-major; either scale may be null)
 __global__ void scale_rows_cols_kernel(const double* __restrict__ Z, int n, int k, const double* __restrict__ rowscale_inv,
@@ -296,7 +297,7 @@ extern "C" int rt_pod_orth(rt_ctx* ctx, const double* X, int64_t n_rows, int64_t
     int k = 0;
     if (sig[0] > floor_sig && room > 0) {
       int cnt = 0;
-      for (int i = 0; i < n; ++i) cnt += (sig[i] >= TWO_PASS_RATIO * sig[0]);
+      for (int i = 0; i < n; ++i) cnt += (sig[i] >= LEVEL_RATIO * sig[0]);
       k = std::min(std::max(1, cnt), room);
     }
     if (k > 0) {

@@ -13,13 +13,15 @@ Algorithm (device work through the C ABI, see include/romtime_hip.h):
            Q = X (D^-1 W_r S_r^-1)          rt_gemm_nn     (back-projection)
 
   deep spectra (a kept mode with sigma_r/sigma_1 < TWO_PASS_RATIO): deflated levels (_pod_deflated) --
-           accept the modes within 1e-2 of the current largest, X <- X - Q (Q^T X) (rt_gemm_tn/_nn),
+           accept the modes within LEVEL_RATIO of the current largest, X <- X - Q (Q^T X) (rt_gemm_tn/_nn),
            Gram + eigensolve again; every level runs on the device.
   passes=2 keeps the alternative rotation + host Jacobi route (rt_host_jacobi_eigh).
 
-One pass reproduces dgesvd's left singular vectors to ~eps (sigma_1/sigma_i)^2; both deep routes bring
-that to ~eps sigma_1/sigma_i, dgesvd's own accuracy (measured against a long-double Jacobi SVD;
-DESIGN.md "POD accuracy").
+One pass reproduces dgesvd's left singular vectors to ~eps (sigma_1/sigma_i)^2.  ``passes=2`` brings that to
+~eps sigma_1/sigma_i, dgesvd's own accuracy; the deflated levels do so at the top of every level and lose up to
+sigma_L/sigma_i <= 1/LEVEL_RATIO = 12.5 towards its bottom (sigma_L: the level's largest singular value).  Measured against
+a long-double SVD by tests/test_pod_truth_gpu.py (helpers tests/svd_cases.py); the ratios per route are in DESIGN.md,
+"POD accuracy" and the "POD against the truth" parity bar.
 """
 from __future__ import annotations
 
@@ -36,6 +38,11 @@ DEVICE_EIG = True      # small eigenproblem on the device (rt_sym_eig_*); False 
 DEVICE_EIG_MAX_N = 1024
 RR_GAP = 1e-4           # smallest eigenvalue gap (relative to lam_1) for which inverse iteration is trusted as is
 TWO_PASS_RATIO = 1e-2  # one Gram pass: vectors good to ~eps (sigma_1/sigma_i)^2 <= 2e-12 above this ratio
+# A deflated level accepts the modes within this ratio of its largest singular value sigma_L.  A Gram pass resolves a mode
+# to eps (sigma_L/sigma_i)^2, sigma_L/sigma_i times what a backward stable SVD delivers: with 1e-2 here the modes at the
+# bottom of a level were up to 18 times (Q^T Q - I: 21 times) outside that (tests/test_pod_truth_gpu.py); 0.08 bounds the
+# loss by 12.5 and costs a level per 1.1 decades of kept spectrum instead of one per two.
+LEVEL_RATIO = 0.08
 
 
 # shapes (n, num, normalize) whose last POD could not use the work enqueued ahead of the eigenvalues (pod_device)
@@ -421,14 +428,14 @@ def pod_device(X: torch.Tensor, num=None, tol=None, normalize=True, passes=None,
     return out
 
 
-MAX_LEVELS = 12
+MAX_LEVELS = 16   # n eps sigma_1 (the floor below) is reached after 13 levels of 1.1 decades
 
 
 def _pod_deflated(X, eig0, colnorm, normalize, num, tol, group, want_vt):
-    """Deep spectra without leaving the device: a Gram pass resolves the modes within TWO_PASS_RATIO of
+    """Deep spectra without leaving the device: a Gram pass resolves the modes within LEVEL_RATIO of
     the current largest singular value to ~eps; those are accepted, projected out of the snapshots
     (X <- X - Q (Q^T X), an O(eps ||X||) perturbation - what dgesvd's backward stability allows too) and the
-    next level starts from a matrix whose largest singular value is >= 100x smaller.  Each level costs a
+    next level starts from a matrix whose largest singular value is >= 12.5x smaller.  Each level costs a
     Gram pass, one small eigensolve and two tall-skinny GEMMs; modes come out with errors ~eps sigma_1 /
     (sigma_i gap), dgesvd's own level (POD accuracy)."""
     n = X.shape[1]
@@ -450,7 +457,7 @@ def _pod_deflated(X, eig0, colnorm, normalize, num, tol, group, want_vt):
         # below n eps sigma_1 the deflated snapshots hold rounding residue, not modes: the numerical rank is reached
         # and the remaining columns of a ``num`` basis stay zero (what the single-pass route returns too)
         floor = n * np.finfo(float).eps * s_acc[0][0] if s_acc else 0.0
-        k = int(min(max(1, np.count_nonzero(sig >= TWO_PASS_RATIO * sig[0])), room)) if sig[0] > floor else 0
+        k = int(min(max(1, np.count_nonzero(sig >= LEVEL_RATIO * sig[0])), room)) if sig[0] > floor else 0
         if k > 0:
             Z = eig.vectors(k)
             src = X if Xc is None else Xc
