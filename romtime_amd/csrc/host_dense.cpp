@@ -78,8 +78,16 @@ extern "C" int rt_host_jacobi_eigh(double* A, int64_t n, double* W, double* lam,
   return RT_OK;
 }
 
-namespace {
-constexpr double DROP_TOLERANCE = 1e-7;   // pod.py:4 (the docstring says 1e-8; the code is 1e-7)
+std::vector<double> rt_sigma(const std::vector<double>& lam) {
+  std::vector<double> s(lam.size());
+  for (size_t i = 0; i < lam.size(); ++i) s[i] = std::sqrt(std::max(lam[i], 0.0));
+  return s;
+}
+
+void rt_energy(const std::vector<double>& s, double total, std::vector<double>& energy) {
+  energy.resize(s.size());
+  double run = 0.0;
+  for (size_t i = 0; i < s.size(); ++i) { run += s[i] * s[i]; energy[i] = run / total; }
 }
 
 // Number of modes `orth` keeps, with the reference's precedence tol > num > DROP_TOLERANCE (pod.py:46-57).
@@ -91,9 +99,44 @@ int rt_truncation_rank(const std::vector<double>& s, const std::vector<double>& 
   } else if (num != 0) {
     r = (int)std::min<int64_t>(num, n);
   } else {
-    for (int i = 0; i < n; ++i) r += (s[i] > DROP_TOLERANCE);
+    for (int i = 0; i < n; ++i) r += (s[i] > RT_DROP_TOLERANCE);
   }
   return r;
+}
+
+bool rt_separated(const std::vector<double>& lam, int k) {
+  const int n = (int)lam.size();
+  const double least = RT_RR_GAP * std::max(lam[0], 1e-300);
+  bool ok = true;   // every comparison positive: a NaN among the gaps rejects
+  for (int i = 0; i < k; ++i) ok = ok && (lam[i] - (i + 1 < n ? lam[i + 1] : 0.0) >= least);
+  return ok;
+}
+
+bool rt_deep(const std::vector<double>& s, int r) { return r > 0 && s[0] > 0.0 && s[r - 1] < RT_TWO_PASS_RATIO * s[0]; }
+
+int rt_level_size(const std::vector<double>& sig, int have, double first_sigma, int room) {
+  const int n = (int)sig.size();
+  // below n eps sigma_1 the deflated snapshots hold rounding residue, not modes: the numerical rank is reached
+  const double floor_sig = have ? n * 2.220446049250313e-16 * first_sigma : 0.0;
+  if (!(sig[0] > floor_sig && room > 0)) return 0;
+  int cnt = 0;
+  for (int i = 0; i < n; ++i) cnt += (sig[i] >= RT_LEVEL_RATIO * sig[0]);
+  return std::min(std::max(1, cnt), room);
+}
+
+int rt_merged_spectrum(const std::vector<double>& s_acc, const std::vector<double>& sig, int k, double total,
+                       std::vector<double>& s_full, std::vector<double>& e_full) {
+  const int n = (int)sig.size(), got = (int)s_acc.size();
+  s_full.assign(n, 0.0);
+  for (int i = 0; i < got && i < n; ++i) s_full[i] = s_acc[i];
+  int tail_n = 0;
+  for (int i = k; i < n && got + tail_n < n; ++i, ++tail_n) s_full[got + tail_n] = sig[i];
+  rt_energy(s_full, total, e_full);
+  return tail_n;
+}
+
+bool rt_levels_done(int r, int got, int k, int n, int levels, int tail_n, double tail0) {
+  return r <= got || k == 0 || got >= n || levels >= RT_MAX_LEVELS || tail_n == 0 || !(tail0 > 0.0);
 }
 
 // Symmetric-definite k x k problem H c = theta S c on the host: S = L L^T, Jacobi on L^-1 H L^-T, back-substitution.

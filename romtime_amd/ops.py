@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, pod_rules
 from ._lib import COL_MAJOR, ROW_MAJOR, Context, RomtimeHipError
 
 _p = C.c_void_p
@@ -96,7 +96,7 @@ def pod_orth(X: torch.Tensor, num=None, tol=None, normalize=True, q_cols=None):
     rc = ctx.lib.rt_pod_orth(ctx.handle, _ptr(X), N, n, ld, lay, int(num or 0), float(tol or 0.0), int(bool(normalize)),
                              _ptr(Q), cap, C.byref(r), s.ctypes.data, energy.ctypes.data, C.byref(levels))
     if rc == _lib.WARN_ZERO_NORM:
-        raise ValueError("array must not contain infs or NaNs (zero-norm snapshot with normalize=True)")
+        raise pod_rules.zero_norm_error()
     ctx.check(rc, "rt_pod_orth")
     return Q[:, : r.value], s, energy, levels.value
 

@@ -31,10 +31,9 @@ import ctypes as C
 import os
 import weakref
 
-import numpy as np
 import torch
 
-from . import _lib, ops, pod
+from . import _lib, ops, pod, pod_rules
 
 _p = C.c_void_p
 
@@ -89,6 +88,27 @@ def _masked_stream(lib, dev, first, count):
 import atexit  # noqa: E402
 
 atexit.register(shutdown)
+
+
+# ---- what the three sequence runners share -----------------------------------------------------------------------------------
+def _checked(X, runner):
+    if X.dim() != 2 or not X.is_cuda or X.dtype != torch.float64:
+        raise _lib.RomtimeHipError(f"{type(runner).__name__} takes 2-D float64 CUDA tensors")
+    return X
+
+
+def _wait_for(waiters, stream):
+    """Every stream of ``waiters`` waits for what ``stream`` holds at this moment (one event).  Towards the runners'
+    streams it orders them after whatever produced a set on the caller's stream: ONCE for a list / tuple, which exists
+    before the run; per set for any other iterable, which may produce a set at the moment it is asked for it.  (Per
+    set on the LEGACY DEFAULT stream that costs the overlap - an event recorded on the null stream completes only when
+    every blocking stream has drained, the CU-masked ones included: 9.6 instead of 5.8 ms per POD of 1e6 x 512 - so a
+    lazy producer should run under a stream of its own, `with torch.cuda.stream(s): ...`.)  Towards the caller's stream,
+    at the end of a run, it makes the results safe to use there."""
+    ev = torch.cuda.Event()
+    ev.record(stream)
+    for st in waiters:
+        st.wait_event(ev)
 
 
 class PodPipeline:
@@ -173,21 +193,18 @@ class PodPipeline:
             item["k0"] = torch.cuda.Event(enable_timing=True)
             item["k0"].record()                                                    # Gram kernels + slab reduction end here
             item["Gbuf"] = Gbuf
-            if self.sR is None:
-                if self.group is not None:      # a one-rank group without forced collectives: nothing to sum
-                    import torch.distributed as dist
+        # the sum over the row slabs: behind the Gram kernels on stream R where there is one (__init__), else in place
+        # on stream G (a one-rank group without forced collectives: nothing to sum, but the call is the same)
+        st = self.sG if self.sR is None else self.sR
+        with torch.cuda.stream(st):
+            if st is not self.sG:
+                st.wait_event(item["k0"])
+            if self.group is not None:
+                import torch.distributed as dist
 
-                    dist.all_reduce(Gbuf, op=dist.ReduceOp.SUM, group=self.group)
-                item["g"] = torch.cuda.Event(enable_timing=True)
-                item["g"].record()
-        if self.sR is not None:
-            import torch.distributed as dist
-
-            with torch.cuda.stream(self.sR):
-                self.sR.wait_event(item["k0"])
                 dist.all_reduce(Gbuf, op=dist.ReduceOp.SUM, group=self.group)
-                item["g"] = torch.cuda.Event(enable_timing=True)
-                item["g"].record()
+            item["g"] = torch.cuda.Event(enable_timing=True)
+            item["g"].record()
 
     def _eig(self, item):
         """Stream E: the n x n eigenproblem of this set - on every rank of a single-GPU run, on ONE rank (set index mod
@@ -231,7 +248,7 @@ class PodPipeline:
             payload = item["payload"]
             item["colnorm"].copy_(payload[n:2 * n])                # handed out: lives on the caller's stream (admit())
             item["Zs"] = payload[2 * n + 2:].view(n, k)
-            head = torch.cat([payload[:n], payload[2 * n:2 * n + 2], item["Gbuf"][-1:]])
+            head = pod.pack_head(payload[:n], payload[2 * n:2 * n + 2], item["Gbuf"][-1:])
             item["head"] = torch.empty(head.numel(), dtype=torch.float64).pin_memory()
             item["head"].copy_(head, non_blocking=True)
             item["_keep2"] = head
@@ -260,25 +277,20 @@ class PodPipeline:
         if item["direct"]:
             return self._regular(item)
         item["b"].synchronize()
-        n, k = item["X"].shape[1], item["k"]
-        head = item["head"].numpy()
-        lam, status, zero_norm, n_rows = head[:n], int(head[n]), int(head[n + 1]), int(round(head[n + 2]))
-        if item["normalize"] and zero_norm:
-            raise ValueError("array must not contain infs or NaNs (zero-norm snapshot with normalize=True)")
-        s = np.sqrt(np.clip(lam, 0.0, None))
-        energy = pod._energy(s)
-        gaps = lam[:k] - lam[1:k + 1] if k < n else np.r_[lam[:k - 1] - lam[1:k], lam[k - 1]]
-        ok = (status == 0 and s[0] > 0 and s[k - 1] >= pod.TWO_PASS_RATIO * s[0]
-              and gaps.min() >= pod.RR_GAP * max(lam[0], 1e-300) and n_rows >= n)
+        head = pod_rules.parse_head(item["head"].numpy(), item["X"].shape[1])
+        if item["normalize"] and head.zero_norm:
+            raise pod_rules.zero_norm_error()
+        r = pod_rules.single_pass_rank(head.lam, head.status, head.n_rows, item["k"], num=item["num"])   # k or None
         self.last_stage_ms = dict(gram_kernel_ms=item["t0"].elapsed_time(item["k0"]),
                                   gram_allreduce_ms=item["t0"].elapsed_time(item["g"]),
                                   eig_chain_ms=item["g"].elapsed_time(item["e"]),
                                   gram_start_to_basis_ms=item["t0"].elapsed_time(item["b"]))
         self.gram_kernel_ms.append(self.last_stage_ms["gram_kernel_ms"])
-        if not ok:
+        if r is None:
             # what pod_device decides after the fact too: this spectrum needs deflated levels / a Rayleigh-Ritz step
             return self._regular(item)
-        return dict(Q=item["Q"], s=s, energy=energy, VT=None, r=k, passes=1, colnorm=item["colnorm"])
+        s = pod_rules.sigma(head.lam)
+        return dict(Q=item["Q"], s=s, energy=pod_rules.energy(s), VT=None, r=r, passes=1, colnorm=item["colnorm"])
 
     # ---- driver -----------------------------------------------------------------------------------------------
     def run(self, snapshot_sets, num, normalize=True, depth=2):
@@ -297,30 +309,16 @@ class PodPipeline:
         it = iter(snapshot_sets)
         self._admitted = 0
         depth = max(depth, self.world + 1)       # enough sets in flight for every rank's eigensolver stream to have one
-
-        def after_producer():
-            ready = torch.cuda.Event()
-            ready.record(main)
-            for st in (self.sG, self.sE, self.sC):
-                if st is not None:
-                    st.wait_event(ready)
-
-        # A list / tuple exists before the run: ONE event orders the pipeline's streams after whatever produced it.  Any
-        # other iterable may produce a set on the caller's stream at the moment it is asked for it: one event per set.
-        # (Per set on the LEGACY DEFAULT stream that costs the overlap - an event recorded on the null stream completes
-        # only when every blocking stream has drained, the CU-masked ones included: 9.6 instead of 5.8 ms per POD of
-        # 1e6 x 512 - so a lazy producer should run under a stream of its own, `with torch.cuda.stream(s): ...`.)
-        materialised = isinstance(snapshot_sets, (list, tuple))
+        streams = [st for st in (self.sG, self.sE, self.sC) if st is not None]
+        materialised = isinstance(snapshot_sets, (list, tuple))     # see _wait_for
         if materialised:
-            after_producer()
+            _wait_for(streams, main)
 
         def admit():
             try:
-                X = next(it)
+                X = _checked(next(it), self)
             except StopIteration:
                 return None
-            if X.dim() != 2 or not X.is_cuda or X.dtype != torch.float64:
-                raise _lib.RomtimeHipError("PodPipeline takes 2-D float64 CUDA tensors")
             item = dict(X=X, num=num, k=int(min(num, X.shape[1])), normalize=bool(normalize), index=self._admitted)
             self._admitted += 1
             n = X.shape[1]
@@ -340,7 +338,7 @@ class PodPipeline:
                 item["Q"] = torch.empty((X.shape[0], item["k"]), dtype=torch.float64, device=X.device)
                 item["colnorm"] = torch.empty(n, dtype=torch.float64, device=X.device)
                 if not materialised:
-                    after_producer()
+                    _wait_for(streams, main)
                 self._gram(item)
                 self._eig(item)
             return item
@@ -363,16 +361,8 @@ class PodPipeline:
             flight.append(cur)
             while len(flight) > depth or (not pending and flight):
                 yield self._finish(flight.popleft())
-        done = torch.cuda.Event()
-        done.record(self.sG)
-        main.wait_event(done)                    # results are safe to use on the caller's stream
-        done2 = torch.cuda.Event()
-        done2.record(self.sE)
-        main.wait_event(done2)
-        if self.sC is not None:
-            done3 = torch.cuda.Event()
-            done3.record(self.sC)
-            main.wait_event(done3)
+        for st in streams:
+            _wait_for([main], st)                # results are safe to use on the caller's stream
 
     def map(self, snapshot_sets, num, normalize=True, depth=2):
         return list(self.run(snapshot_sets, num, normalize=normalize, depth=depth))
@@ -411,13 +401,12 @@ class PodLanes:
 
     def _enqueue(self, item, lane):
         X, k, normalize = item["X"], item["k"], item["normalize"]
-        n = X.shape[1]
         with self.ctx[lane].use(self.streams[lane]):
             # one host call for the whole chain (rt_pod_enqueue): with a Python call per kernel the host, not the chip,
             # decided how many chains were in flight
             Q, lam_d, status2, colnorm, keep = ops.pod_enqueue(X, k, normalize)
-            head = torch.cat([lam_d, status2.to(torch.float64)])
-            item["head"] = torch.empty(n + 2, dtype=torch.float64).pin_memory()
+            head = pod.pack_head(lam_d, status2)       # status2: eigensolver status, zero-norm flag
+            item["head"] = torch.empty(head.numel(), dtype=torch.float64).pin_memory()
             item["head"].copy_(head, non_blocking=True)
             item["Q"], item["colnorm"] = Q, colnorm
             item["_keep"] = (keep, head, lam_d, status2)
@@ -438,23 +427,20 @@ class PodLanes:
         if item["direct"]:
             return self._regular(item)
         item["done"].synchronize()
-        n, k = item["X"].shape[1], item["k"]
-        head = item["head"].numpy()
-        lam, status, zero_norm = head[:n], int(head[n]), int(head[n + 1])
-        if item["normalize"] and zero_norm:
-            raise ValueError("array must not contain infs or NaNs (zero-norm snapshot with normalize=True)")
-        s = np.sqrt(np.clip(lam, 0.0, None))
-        energy = pod._energy(s)
-        r = pod.truncation_rank(s, energy, num=item["num"], tol=item["tol"])     # orth's own rule, after the fact
-        if status != 0 or not (1 <= r <= k) or not s[0] > 0 or item["X"].shape[0] < n:
+        N, n = item["X"].shape
+        head = pod_rules.parse_head(item["head"].numpy(), n, n_rows=N)
+        if item["normalize"] and head.zero_norm:
+            raise pod_rules.zero_norm_error()
+        # orth's own truncation rule, after the fact; None: the kept modes are deep or clustered (deflated levels /
+        # Rayleigh-Ritz), more than were enqueued, or the eigensolve has to be done again
+        r = pod_rules.single_pass_rank(head.lam, head.status, head.n_rows, item["k"], num=item["num"], tol=item["tol"])
+        if r is None:
             return self._regular(item)
-        gaps = lam[:r] - lam[1:r + 1] if r < n else np.r_[lam[:r - 1] - lam[1:r], lam[r - 1]]
-        if s[r - 1] < pod.TWO_PASS_RATIO * s[0] or gaps.min() < pod.RR_GAP * max(lam[0], 1e-300):
-            return self._regular(item)           # deep or clustered among the kept modes: deflated levels / Rayleigh-Ritz
-        Q = item["Q"] if r == k else item["Q"][:, :r]
+        Q = item["Q"] if r == item["k"] else item["Q"][:, :r]
         for t in (item["Q"], item["colnorm"]):                      # allocated under the lane's stream, used by the caller's
             t.record_stream(torch.cuda.current_stream(self.device))
-        return dict(Q=Q, s=s, energy=energy, VT=None, r=r, passes=1, colnorm=item["colnorm"])
+        s = pod_rules.sigma(head.lam)
+        return dict(Q=Q, s=s, energy=pod_rules.energy(s), VT=None, r=r, passes=1, colnorm=item["colnorm"])
 
     def run(self, snapshot_sets, num=None, normalize=True, tol=None, cap=64):
         """Generator over the results (dicts as ``pod.pod_device`` returns) of ``orth(X, num=num, tol=tol,
@@ -466,30 +452,23 @@ class PodLanes:
         it = iter(snapshot_sets)
         pending = collections.deque()
         admitted = 0
-        materialised = isinstance(snapshot_sets, (list, tuple))     # see PodPipeline._run
+        materialised = isinstance(snapshot_sets, (list, tuple))     # see _wait_for
         if materialised:
-            ready = torch.cuda.Event()
-            ready.record(main)
-            for st in self.streams:
-                st.wait_event(ready)
+            _wait_for(self.streams, main)
 
         def admit():
             nonlocal admitted
             try:
-                X = next(it)
+                X = _checked(next(it), self)
             except StopIteration:
                 return False
-            if X.dim() != 2 or not X.is_cuda or X.dtype != torch.float64:
-                raise _lib.RomtimeHipError("PodLanes takes 2-D float64 CUDA tensors")
             n = X.shape[1]
             k = int(min(num, n)) if (num and not tol) else int(min(cap, n))
             item = dict(X=X, num=num, tol=tol, k=k, normalize=bool(normalize), direct=not (3 <= n <= 512))
             if not item["direct"]:
                 lane = admitted % len(self.streams)
                 if not materialised:
-                    ready = torch.cuda.Event()   # a lazy iterable produces this set on the caller's stream just now
-                    ready.record(main)
-                    self.streams[lane].wait_event(ready)
+                    _wait_for([self.streams[lane]], main)
                 self._enqueue(item, lane)
             admitted += 1
             pending.append(item)
@@ -502,10 +481,8 @@ class PodLanes:
             out = self._finish(pending.popleft())
             admit()                                # the lane just freed takes the next set
             yield out
-        done = torch.cuda.Event()
         for st in self.streams:                    # later work on the caller's stream sees every Q
-            done.record(st)
-            main.wait_event(done)
+            _wait_for([main], st)
 
     def map(self, snapshot_sets, num=None, normalize=True, tol=None, cap=64):
         return list(self.run(snapshot_sets, num=num, normalize=normalize, tol=tol, cap=cap))
@@ -588,11 +565,9 @@ class PodWorkers:
 
         def admit():
             try:
-                X = next(it)
+                X = _checked(next(it), self)
             except StopIteration:
                 return False
-            if X.dim() != 2 or not X.is_cuda or X.dtype != torch.float64:
-                raise _lib.RomtimeHipError("PodWorkers takes 2-D float64 CUDA tensors")
             ready = torch.cuda.Event()
             ready.record(main)
             pending.append((X, self.pool.submit(self._job, X, ready, kwargs)))

@@ -22,6 +22,10 @@ One pass reproduces dgesvd's left singular vectors to ~eps (sigma_1/sigma_i)^2. 
 sigma_L/sigma_i <= 1/LEVEL_RATIO = 12.5 towards its bottom (sigma_L: the level's largest singular value).  Measured against
 a long-double SVD by tests/test_pod_truth_gpu.py (helpers tests/svd_cases.py); the ratios per route are in DESIGN.md,
 "POD accuracy" and the "POD against the truth" parity bar.
+
+Every decision taken from a spectrum - the constants above, the truncation rank, deep or shallow, the eigenvalue-gap
+rule, what a level accepts and when the levels stop - is stated once in pod_rules.py (pure NumPy) and used from here and
+from pipeline.py; rt_pod_orth has the same rules in csrc/host_dense.{h,cpp}.
 """
 from __future__ import annotations
 
@@ -31,18 +35,12 @@ import threading
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, pod_rules
+from .pod_rules import DROP_TOLERANCE, LEVEL_RATIO, MAX_LEVELS, RR_GAP, TWO_PASS_RATIO, truncation_rank  # noqa: F401
+from .pod_rules import energy as _energy
 
-DROP_TOLERANCE = 1e-7  # pod.py:4 (the reference's docstring says 1e-8; the code is 1e-7)
 DEVICE_EIG = True      # small eigenproblem on the device (rt_sym_eig_*); False = host LAPACK
 DEVICE_EIG_MAX_N = 1024
-RR_GAP = 1e-4           # smallest eigenvalue gap (relative to lam_1) for which inverse iteration is trusted as is
-TWO_PASS_RATIO = 1e-2  # one Gram pass: vectors good to ~eps (sigma_1/sigma_i)^2 <= 2e-12 above this ratio
-# A deflated level accepts the modes within this ratio of its largest singular value sigma_L.  A Gram pass resolves a mode
-# to eps (sigma_L/sigma_i)^2, sigma_L/sigma_i times what a backward stable SVD delivers: with 1e-2 here the modes at the
-# bottom of a level were up to 18 times (Q^T Q - I: 21 times) outside that (tests/test_pod_truth_gpu.py); 0.08 bounds the
-# loss by 12.5 and costs a level per 1.1 decades of kept spectrum instead of one per two.
-LEVEL_RATIO = 0.08
 
 
 # shapes (n, num, normalize) whose last POD could not use the work enqueued ahead of the eigenvalues (pod_device)
@@ -72,18 +70,6 @@ def stage_timings() -> dict:
         if pend["levels"] is not None:
             LAST_TIMINGS["levels"] = pend["levels"]
     return LAST_TIMINGS
-
-
-def truncation_rank(s, energy, num=None, tol=None) -> int:
-    """Number of modes kept, with the reference's precedence (pod.py:46-57).
-
-    ``energy < tol`` is strict, so the mode that crosses ``tol`` is excluded; the energy curve is
-    non-decreasing and ``s`` non-increasing, hence every mask is a prefix."""
-    if tol:
-        return int(np.count_nonzero(energy < tol))
-    if num:
-        return int(min(num, len(s)))
-    return int(np.count_nonzero(s > DROP_TOLERANCE))
 
 
 def _profiling(ctx) -> bool:
@@ -145,11 +131,6 @@ def jacobi_eigh(G: np.ndarray, max_sweeps: int = 40):
     return lam, W
 
 
-def _energy(s):
-    ev = np.power(s, 2)
-    return np.cumsum(ev) / np.sum(ev)
-
-
 def _inv_or_zero(s):
     out = np.zeros_like(s)
     nz = s > 0
@@ -160,8 +141,8 @@ def _inv_or_zero(s):
 class _SmallEig:
     """Eigen-decomposition of the n x n Gram matrix: all eigenvalues (host array, descending) at once,
     leading eigenvectors on request (device, n x k).  3 <= n <= 1024 runs on the device
-    (rt_sym_eig_values / rt_sym_eig_vectors, Rayleigh-Ritz polish on G when kept eigenvalues are
-    closer than RR_GAP * lam_1); other sizes use host LAPACK."""
+    (rt_sym_eig_values / rt_sym_eig_vectors, Rayleigh-Ritz polish on G when the kept eigenvalues are
+    not ``pod_rules.separated``); other sizes use host LAPACK.  ``head``: the parsed pod_rules.Head."""
 
     def __init__(self, G: torch.Tensor, extra=(), group=None, ahead=None):
         """``ahead(self)``: device work the caller wants enqueued BEFORE the eigenvalues reach the host (it may
@@ -184,13 +165,14 @@ class _SmallEig:
                     f, _ = _share(self.n, self.group, rank=r)
                     self.lam_d[f:f + cnt] = piece[:cnt]
                 status = torch.stack([piece[cnt] for piece in pieces]).max().reshape(1)
-            head = torch.cat([self.lam_d, status.to(torch.float64)] + [e.to(torch.float64).reshape(-1) for e in extra])
+            head = pack_head(self.lam_d, status, *extra)
             if ahead is None:
                 head = head.cpu().numpy()  # the one device->host transfer of the step
             else:
                 head = _fetch_beside(head, lambda: ahead(self))
-            self.lam, self.extra = head[: self.n], head[self.n + 1:]
-            if int(head[self.n]) != 0:
+            self.head = pod_rules.parse_head(head, self.n)
+            self.lam = self.head.lam
+            if self.head.status != 0:
                 # A hand-off of the cooperative tridiagonalisation hit its wall-clock bound: some of its workgroups
                 # were not resident (another stream or process held CUs).  Nothing computed from it is used.  This
                 # ctx (one per thread and device) leaves the one-XCD form for good and the decomposition is redone
@@ -210,8 +192,9 @@ class _SmallEig:
                 self.on_device, self.group = False, None
         if not self.on_device:
             Gh = G.cpu().numpy()
-            self.extra = np.concatenate([np.atleast_1d(e.cpu().numpy()).astype(float) for e in extra]) if extra else np.zeros(0)
+            extra = [np.atleast_1d(e.cpu().numpy()).astype(float) for e in extra]
             self.lam, self.W = _eigh_desc(Gh)
+            self.head = pod_rules.parse_head(np.concatenate([self.lam, [0.0]] + extra), self.n)
 
     def raw_vectors(self, k: int) -> torch.Tensor:
         """Inverse-iteration eigenvectors of the k largest eigenvalues as the device computes them (no host data
@@ -231,12 +214,9 @@ class _SmallEig:
         return Z
 
     def well_separated(self, k: int) -> bool:
-        """Inverse iteration resolves an eigenvector to ~eps ||G|| / gap: with every gap among the kept
-        eigenvalues (and to the first discarded one) above RR_GAP * lam_1 that is <= 2e-12 and the
-        vectors are used as they are; closer eigenvalues get a k x k Rayleigh-Ritz step on G (``vectors``)."""
-        n, lam = self.n, self.lam
-        gaps = lam[:k] - lam[1:k + 1] if k < n else np.r_[lam[:k - 1] - lam[1:k], lam[k - 1]]
-        return bool(gaps.min() >= RR_GAP * max(lam[0], 1e-300))
+        """The inverse-iteration vectors of the k largest eigenvalues are used as they are (pod_rules.separated);
+        otherwise ``vectors`` adds a k x k Rayleigh-Ritz step on G."""
+        return pod_rules.separated(self.lam, k)
 
     def vectors(self, k: int) -> torch.Tensor:
         """n x k eigenvectors of the k largest eigenvalues (must be called before any other device
@@ -258,6 +238,12 @@ class _SmallEig:
         if np.abs(theta - lam[:k]).max() > 1e-9 * max(lam[0], 1e-300):
             raise _lib.RomtimeHipError("device eigenvectors failed the Rayleigh-Ritz cross-check")
         return ops.gemm_nn(Z, ops.to_device(C, Z.device))
+
+
+def pack_head(lam, *rest):
+    """The head on the device (layout: pod_rules.Head): ``lam`` and the tensors that follow it in Head's order (any
+    dtype, one or more fields each) as one float64 tensor - one transfer brings it to the host (pod_rules.parse_head)."""
+    return torch.cat([lam] + [t.to(torch.float64).reshape(-1) for t in rest])
 
 
 _PINNED_TLS = threading.local()   # per thread: concurrent PODs (pipeline.PodWorkers) must not share a staging buffer
@@ -372,16 +358,13 @@ def pod_device(X: torch.Tensor, num=None, tol=None, normalize=True, passes=None,
     eig = _SmallEig(G, extra=(flag, Gbuf[n * n:]), group=group, ahead=ahead if k_ahead else None)
     if prof and not k_ahead:
         ev[2].record()
-    if normalize and int(eig.extra[0]) != 0:
-        # the reference divides by a zero norm and scipy.linalg.svd then rejects the NaNs (pod.py:32-38)
-        raise ValueError("array must not contain infs or NaNs (zero-norm snapshot with normalize=True)")
-    lam = eig.lam
-    s = np.sqrt(np.clip(lam, 0.0, None))
+    if normalize and eig.head.zero_norm != 0:
+        raise pod_rules.zero_norm_error()
+    s = pod_rules.sigma(eig.lam)
     energy = _energy(s)
     r = truncation_rank(s, energy, num=num, tol=tol)
-    deep = r > 0 and s[0] > 0 and s[r - 1] < TWO_PASS_RATIO * s[0]
     if passes is None:
-        passes = "deflate" if deep else 1
+        passes = "deflate" if pod_rules.deep(s, r) else 1
     _AHEAD_DROPPED[ahead_key] = bool(passes != 1 or r != ahead_key[1])
 
     if passes == 1:
@@ -400,7 +383,7 @@ def pod_device(X: torch.Tensor, num=None, tol=None, normalize=True, passes=None,
         Y = ops.gemm_nn(X, (W / colnorm[:, None] if normalize else W).contiguous())
         G2 = _allreduce(ops.gram(Y), group).cpu().numpy()
         lam2, W2 = jacobi_eigh(G2)
-        s = np.sqrt(np.clip(lam2, 0.0, None))
+        s = pod_rules.sigma(lam2)
         energy = _energy(s)
         r = truncation_rank(s, energy, num=num, tol=tol)
         T2 = W2[:, :r] * _inv_or_zero(s[:r])
@@ -411,7 +394,7 @@ def pod_device(X: torch.Tensor, num=None, tol=None, normalize=True, passes=None,
     else:
         raise ValueError(f"passes must be None, 1, 2 or 'deflate', not {passes!r}")
     # more snapshots than DoFs: the thin SVD of the reference has only min(N, n) singular values (pod.py:38)
-    n_rows = int(round(float(eig.extra[1])))  # global row count (summed with G over the ranks)
+    n_rows = eig.head.n_rows  # global row count (summed with G over the ranks)
     if n_rows < n:
         s, energy, r = s[:n_rows], energy[:n_rows], min(r, n_rows)
         Q = Q[:, :r].contiguous()
@@ -428,12 +411,9 @@ def pod_device(X: torch.Tensor, num=None, tol=None, normalize=True, passes=None,
     return out
 
 
-MAX_LEVELS = 16   # n eps sigma_1 (the floor below) is reached after 13 levels of 1.1 decades
-
-
 def _pod_deflated(X, eig0, colnorm, normalize, num, tol, group, want_vt):
     """Deep spectra without leaving the device: a Gram pass resolves the modes within LEVEL_RATIO of
-    the current largest singular value to ~eps; those are accepted, projected out of the snapshots
+    the current largest singular value to ~eps; those are accepted (pod_rules.level_size), projected out of the snapshots
     (X <- X - Q (Q^T X), an O(eps ||X||) perturbation - what dgesvd's backward stability allows too) and the
     next level starts from a matrix whose largest singular value is >= 12.5x smaller.  Each level costs a
     Gram pass, one small eigensolve and two tall-skinny GEMMs; modes come out with errors ~eps sigma_1 /
@@ -451,13 +431,9 @@ def _pod_deflated(X, eig0, colnorm, normalize, num, tol, group, want_vt):
     levels = 0
     while True:
         levels += 1
-        sig = np.sqrt(np.clip(eig.lam, 0.0, None))
+        sig = pod_rules.sigma(eig.lam)
         have = sum(len(x) for x in s_acc)
-        room = (cap if cap else n) - have
-        # below n eps sigma_1 the deflated snapshots hold rounding residue, not modes: the numerical rank is reached
-        # and the remaining columns of a ``num`` basis stay zero (what the single-pass route returns too)
-        floor = n * np.finfo(float).eps * s_acc[0][0] if s_acc else 0.0
-        k = int(min(max(1, np.count_nonzero(sig >= LEVEL_RATIO * sig[0])), room)) if sig[0] > floor else 0
+        k = pod_rules.level_size(sig, s_acc[0][0] if s_acc else None, (cap if cap else n) - have, n)
         if k > 0:
             Z = eig.vectors(k)
             src = X if Xc is None else Xc
@@ -468,13 +444,9 @@ def _pod_deflated(X, eig0, colnorm, normalize, num, tol, group, want_vt):
             Q_acc.append(Ql)
             if want_vt:
                 W_acc.append(Z.cpu().numpy())
-        got = sum(len(x) for x in s_acc)
-        tail = sig[k:k + (n - got)]
-        s_full = np.concatenate(s_acc + [tail, np.zeros(max(0, n - got - len(tail)))])
-        ev = np.power(s_full, 2)
-        energy = np.cumsum(ev) / total
+        s_full, energy, tail = pod_rules.merged_spectrum(s_acc, sig, k, total)
         r = truncation_rank(s_full, energy, num=num, tol=tol)
-        if r <= got or k == 0 or got >= n or levels >= MAX_LEVELS or tail.size == 0 or tail[0] <= 0.0:
+        if pod_rules.levels_done(r, have + k, k, n, levels, tail):
             break
         # deflate: X <- X - Q (Q^T X), twice (classical Gram-Schmidt needs the second sweep; taking its
         # coefficients from the k x k matrix Q^T Q instead, C = (2I - Q^T Q) Q^T X, saves a pass over the snapshots

@@ -2,6 +2,9 @@
 // tests/test_host_sanitizers.py with  g++ -fsanitize=address,undefined -fno-sanitize-recover=all  and executed; any heap /
 // stack overrun, use of uninitialised-by-construction memory the sanitizers see, signed overflow or misaligned access
 // aborts the run.  The numerical checks double as known-answer tests of the three helpers.
+//
+// With a file name as argument it prints instead what the POD rules of host_dense.h decide on the cases of that file, one
+// line per case, for tests/test_pod_rules_cpu.py to hold against romtime_amd/pod_rules.py (formats: `decide` below).
 #include <cmath>
 #include <cstdio>
 #include <random>
@@ -14,7 +17,52 @@ static int fail(const char* what, double v) {
   return 1;
 }
 
-int main() {
+// A case is one line "n num tol k status n_rows room first lam[0] .. lam[n-1]" (doubles as hex floats; first < 0: no mode
+// accepted yet, else one mode with that singular value was).  Its answer is one line
+//   r deep separated(r) verdict | level_size r_after stop | s[0..n) | energy[0..n)
+// r .. verdict: `lam` as the spectrum of a whole set - truncation rank, rt_deep, rt_separated (0 when r == 0) and whether
+// k single-pass vectors enqueued ahead may be handed out (r, or -1); level_size .. energy: `lam` as the spectrum of a
+// deflated level with `room` columns left - what it accepts, the merged spectrum after it, the rank on that, the stop flag.
+// The verdict is composed HERE from the library's pieces (rank, sigma, rt_separated) and the shallow bound written out: the
+// library has no such function (what rt_pod_enqueue put ahead is judged in Python), so that column holds
+// pod_rules.single_pass_rank against this restatement and says nothing about shipped C code; the other columns do.
+static int decide(const char* path) {
+  std::FILE* f = std::fopen(path, "r");
+  if (!f) return fail("cannot open the case file", 0);
+  int n, k, status, room;
+  long num, n_rows;
+  double tol, first;
+  while (std::fscanf(f, "%d %ld %la %d %d %ld %d %la", &n, &num, &tol, &k, &status, &n_rows, &room, &first) == 8) {
+    std::vector<double> lam(n), energy, s_full, e_full;
+    for (double& v : lam)
+      if (std::fscanf(f, "%la", &v) != 1) return fail("short case", n);
+    const std::vector<double> s = rt_sigma(lam);
+    double total = 0.0;
+    for (double v : s) total += v * v;
+    rt_energy(s, total, energy);
+    const int r = rt_truncation_rank(s, energy, num, tol);
+    const bool sep = r > 0 && rt_separated(lam, r);
+    const bool ok = status == 0 && n_rows >= n && 1 <= r && r <= k && s[0] > 0.0 && s[r - 1] >= RT_TWO_PASS_RATIO * s[0] && sep;
+    std::vector<double> s_acc;
+    if (first >= 0.0) { s_acc.push_back(first); total = first * first + total; }
+    const int have = (int)s_acc.size();
+    const int kl = rt_level_size(s, have, have ? s_acc[0] : 0.0, room);
+    s_acc.insert(s_acc.end(), s.begin(), s.begin() + kl);
+    const int tail_n = rt_merged_spectrum(s_acc, s, kl, total, s_full, e_full);
+    const int r_after = rt_truncation_rank(s_full, e_full, num, tol);
+    const bool stop = rt_levels_done(r_after, have + kl, kl, n, 1, tail_n, tail_n > 0 ? s[kl] : 0.0);
+    std::printf("%d %d %d %d | %d %d %d |", r, (int)rt_deep(s, r), (int)sep, ok ? r : -1, kl, r_after, (int)stop);
+    for (double v : s_full) std::printf(" %a", v);
+    std::printf(" |");
+    for (double v : e_full) std::printf(" %a", v);
+    std::printf("\n");
+  }
+  std::fclose(f);
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1) return decide(argv[1]);
   std::mt19937_64 rng(7);
   std::normal_distribution<double> nd(0.0, 1.0);
   for (int n : {1, 2, 3, 7, 32, 65}) {

@@ -19,7 +19,7 @@ import numpy as np
 
 LD = np.longdouble
 EPS = float(np.finfo(np.float64).eps)        # 2.2e-16
-TWO_PASS_RATIO = 1e-2                         # restated from romtime_amd/pod.py and csrc/pod_orth.hip
+TWO_PASS_RATIO = 1e-2                         # restated from romtime_amd/pod_rules.py and csrc/host_dense.h
 LEVEL_RATIO = 0.08                            # what a deflated level accepts, restated from the same two places
 DROP_TOLERANCE = 1e-7
 

@@ -109,6 +109,47 @@ def test_lanes_match_single_pods_and_oracle():
         lanes.map([Z], num=3, normalize=True)
 
 
+def test_runners_hand_every_rejected_set_to_the_regular_route():
+    """The rejections of ``pod_rules.single_pass_rank`` that the tests above do not reach: of four sets with num = 4 and
+    normalize=False - (a) shallow and separated, (b) two equal kept singular values, (c) deep, (d) fewer rows than columns -
+    PodLanes and PodPipeline keep (a) and recompute the other three with ``pod.pod_device``, whose result they hand out
+    as it is."""
+    from romtime_amd import ops, pod
+    from romtime_amd.pipeline import PodLanes, PodPipeline
+
+    rng = np.random.RandomState(23)
+    n, k = 48, 4
+
+    def build(N, s):
+        U, _ = np.linalg.qr(rng.standard_normal((N, len(s))))
+        V, _ = np.linalg.qr(rng.standard_normal((n, len(s))))
+        return (U * s) @ V.T
+
+    i = np.arange(n)
+    mats = [build(4096, 2.0 ** -i), build(4096, np.r_[1.0, 0.5, 2.0 ** -i[1:n - 1]]),
+            build(4096, np.maximum(10.0 ** (-3.0 * i), 1e-15)), build(40, 2.0 ** -i[:40])]
+    dev = [ops.to_device(m) for m in mats]
+    for runner in (PodLanes(), PodPipeline(small_set=0)):
+        outs = runner.map(dev, num=k, normalize=False)
+        assert runner.recomputed == 3, type(runner).__name__
+        # in the runner's order: pod_device's look-ahead of (d) depends on what the POD of this shape before it, (c), needed
+        for Xd, out in list(zip(dev, outs))[1:]:
+            single = pod.pod_device(Xd, num=k, normalize=False)
+            assert out["r"] == single["r"] and out["passes"] == single["passes"]
+            assert np.array_equal(out["Q"].cpu().numpy(), single["Q"].cpu().numpy())
+            assert np.array_equal(out["s"], single["s"]) and np.array_equal(out["energy"], single["energy"])
+        out, single = outs[0], pod.pod_device(dev[0], num=k, normalize=False)
+        Qo, so, eo = oracle.orth(mats[0], num=k, normalize=False)
+        bar = 2e-13 * so[0] + 8 * EPS * so[0] ** 2 / np.maximum(so, 1e-300)
+        assert out["r"] == k and out["passes"] == 1 and np.all(np.abs(out["s"] - so) <= bar)
+        np.testing.assert_allclose(out["energy"], eo, rtol=1e-10)
+        Q = out["Q"].cpu().numpy()
+        assert np.abs(Q.T @ Q - np.eye(k)).max() < 1e-10
+        _same_columns(Q, single["Q"].cpu().numpy(), 1e-11)
+        _same_columns(Q, Qo, 1e-9)
+        runner.close()
+
+
 def test_cu_partition_abi():
     """rt_stream_create_cu_range / "cu_limit": argument checks, and kernels on a masked stream give the same numbers."""
     import ctypes as C
