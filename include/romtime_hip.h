@@ -79,7 +79,8 @@ int rt_last_gemm_ms(rt_ctx* ctx, double* ms);
 /* Event counters kept on the device by the kernels themselves (nothing on the hot path waits for them); reading one
  * synchronises the ctx stream.  Names: "eig_timeouts" (hand-offs of the small eigensolver that hit their wall-clock
  * bound: results of that call were invalid and the caller took another route), "eig_one_xcd" / "eig_general_form"
- * (tridiagonalisations that ran each hand-off form), "gram_off_xcd" (workgroups of the snapshot Gram kernel that ran on
+ * (tridiagonalisations that ran each hand-off form), "eig_wide_form" (tridiagonalisations of 1024 < n <= 2048, which hand
+ * nothing off: every dependency is a kernel boundary), "gram_off_xcd" (workgroups of the snapshot Gram kernel that ran on
  * another XCD than the one their K range was laid out for: should stay 0), "sweep_newton_iterations", "sweep_restarts",
  * "sweep_lu_fallbacks", "sweep_solves" (the four numbers of rt_last_sweep_stats), "sweep_gmres_iterations" (GMRES inner
  * iterations of the most recent sweep, RT_SOLVER_GMRES), "sweep_gmres_unconverged" (its systems that GMRES left with
@@ -112,7 +113,7 @@ int rt_gram_scale(rt_ctx* ctx, double* G, int64_t n, double* colnorm, int normal
 /* The whole of `orth` (pod.py:7-62) in one call, for hosts that bind this library without the Python layer: column
  * norms (normalize != 0), Gram matrix, all singular values, energy curve, truncation with the reference's precedence
  * (tol != 0: energy < tol, strict; else num != 0: first num; else sigma > 1e-7), basis.  X: n_rows x n_cols DEVICE matrix
- * (ld, layout), n_cols <= 1024.  Q: DEVICE buffer n_rows x q_cols row-major; on return its first *r_out columns are the
+ * (ld, layout), n_cols <= 2048 (RT_ERR_UNSUPPORTED beyond).  Q: DEVICE buffer n_rows x q_cols row-major; on return its first *r_out columns are the
  * basis (the others are zero or unspecified); if the rule keeps more than q_cols modes the call returns RT_ERR_ARG with
  * *r_out = the number needed.  s_host / energy_host: HOST arrays of min(n_rows, n_cols) entries - ALL singular values and
  * the whole energy curve, as the reference returns them.  *levels_out (may be NULL): Gram passes taken (1 = single pass;
@@ -338,12 +339,17 @@ int rt_p1_local_assembly(rt_ctx* ctx, int kind, int64_t nx, const int64_t* rows,
                          int64_t n_states, const double* h, const double* coef, int state_mode, const double* state,
                          double* out);
 
-/* ---- small symmetric eigenproblem of the Gram matrix, on the device (3 <= n <= 1024) ---------- */
+/* ---- small symmetric eigenproblem of the Gram matrix, on the device (3 <= n <= 2048) ---------- */
 /* Householder tridiagonalisation (32 cooperating workgroups, 128 for n > 512; matrix resident in LDS) + Sturm
  * multisection:
  * lam (n, device) = all eigenvalues of the symmetric G (n x n row-major, not modified), DESCENDING.
  * status (device int, may be NULL): 0, or 1 if the inter-workgroup hand-off timed out (results
- * invalid).  Replaces the eigenvalue half of LAPACK's work inside scipy.linalg.svd (pod.py:38). */
+ * invalid).  Replaces the eigenvalue half of LAPACK's work inside scipy.linalg.svd (pod.py:38).
+ * 1024 < n <= 2048 (since version 350) takes the wide route: the work copy of G lives in the ctx's composite arena
+ * (2 n^2 doubles with the reflectors: 64 MB at the limit) and the reduction is about 2 n launches on the ctx stream, one
+ * per dependency - no workgroup waits for another, so it needs no co-resident team, cannot time out (status is 0) and
+ * gives the same bits on a CU-masked stream as on the whole chip; counter "eig_wide_form".  All three entry points
+ * below take 3 <= n <= 2048; n > 2048 returns RT_ERR_UNSUPPORTED. */
 int rt_sym_eig_values(rt_ctx* ctx, const double* G, int64_t n, double* lam, int* status);
 /* The same, but only the eigenvalues with descending index in [first, first + count) are searched and written
  * (lam[first .. first+count)); the tridiagonalisation is complete either way.  For a row-sharded POD every rank

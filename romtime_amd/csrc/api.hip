@@ -165,7 +165,7 @@ int rt_func_lds(rt_ctx* ctx, const void* fn, int bytes) {
 
 extern "C" {
 
-int rt_version(void) { return 340; }  // 340: rt_trajectory_errors; 330: rt_gmres_batched, rt_ctx_set_reduced_solver, counters sweep_gmres_*; 320: rt_gram_plan_info; 310: option gram_pace (paced / one-launch Gram); 300 (round 3): rt_dense_solve_multi, RT_P1_LOAD_P2; 210: rt_tracked_solve_batched, rt_pod_enqueue, options eig_xcd, counter gram_off_xcd
+int rt_version(void) { return 350; }  // 350: rt_sym_eig_* and rt_pod_orth take n <= 2048 (wide tridiagonalisation), counter eig_wide_form; 340: rt_trajectory_errors; 330: rt_gmres_batched, rt_ctx_set_reduced_solver, counters sweep_gmres_*; 320: rt_gram_plan_info; 310: option gram_pace (paced / one-launch Gram); 300 (round 3): rt_dense_solve_multi, RT_P1_LOAD_P2; 210: rt_tracked_solve_batched, rt_pod_enqueue, options eig_xcd, counter gram_off_xcd
 
 int rt_ctx_create(rt_ctx** out, int device) {
   if (!out) return RT_ERR_ARG;
@@ -297,7 +297,8 @@ int rt_ctx_get_counter(rt_ctx* ctx, const char* name, int64_t* value) {
       {"eig_timeouts", RT_CNT_EIG_TIMEOUT}, {"eig_general_form", RT_CNT_EIG_GENERAL_FORM},
       {"eig_one_xcd", RT_CNT_EIG_ONE_XCD}, {"gram_off_xcd", RT_CNT_GRAM_OFF_XCD}, {"sweep_newton_iterations", RT_CNT_NS_ITER},
       {"sweep_restarts", RT_CNT_NS_RESTART}, {"sweep_lu_fallbacks", RT_CNT_LU_FALLBACK}, {"sweep_solves", RT_CNT_SOLVES},
-      {"sweep_gmres_iterations", RT_CNT_GMRES_ITER}, {"sweep_gmres_unconverged", RT_CNT_GMRES_UNCONVERGED}};
+      {"sweep_gmres_iterations", RT_CNT_GMRES_ITER}, {"sweep_gmres_unconverged", RT_CNT_GMRES_UNCONVERGED},
+      {"eig_wide_form", RT_CNT_EIG_WIDE_FORM}};
   for (const auto& t : table)
     if (key == t.name) {
       long host = 0;

@@ -7,7 +7,7 @@
 
 #include "../../include/romtime_hip.h"
 
-constexpr int RT_N_COUNTERS = 10;
+constexpr int RT_N_COUNTERS = 11;
 
 struct rt_ctx {
   int device = 0;
@@ -59,7 +59,8 @@ enum {
   RT_CNT_LU_FALLBACK = 6,       // ... systems handed to the pivoted LU
   RT_CNT_SOLVES = 7,            // ... systems solved
   RT_CNT_GMRES_ITER = 8,        // ... GMRES inner iterations (RT_SOLVER_GMRES)
-  RT_CNT_GMRES_UNCONVERGED = 9  // ... systems GMRES left with info != 0
+  RT_CNT_GMRES_UNCONVERGED = 9, // ... systems GMRES left with info != 0
+  RT_CNT_EIG_WIDE_FORM = 10     // tridiagonalisations that took the wide route (1024 < n <= 2048, one launch per dependency)
 };
 
 #define RT_TRY(expr)                 \

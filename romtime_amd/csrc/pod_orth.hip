@@ -221,8 +221,8 @@ extern "C" int rt_pod_orth(rt_ctx* ctx, const double* X, int64_t n_rows, int64_t
   RT_ARG_CHECK(ctx, X && Q && r_out && s_host && energy_host && n_rows >= 1 && n_cols >= 1 && q_cols >= 0 && num >= 0);
   RT_ARG_CHECK(ctx, layout == RT_ROW_MAJOR || layout == RT_COL_MAJOR);
   RT_ARG_CHECK(ctx, ld >= (layout == RT_ROW_MAJOR ? n_cols : n_rows));
-  if (n_cols > 1024) {
-    ctx->err = "rt_pod_orth: more than 1024 snapshots (the device eigensolver's limit; use the pieces with a host eigensolver)";
+  if (n_cols > 2048) {
+    ctx->err = "rt_pod_orth: more than 2048 snapshots (the device eigensolver's limit; use the pieces with a host eigensolver)";
     return RT_ERR_UNSUPPORTED;
   }
   const int n = (int)n_cols;

@@ -1,4 +1,4 @@
-// Symmetric eigensolver for the small n x n Gram matrix of the POD (3 <= n <= 1024), on the device:
+// Symmetric eigensolver for the small n x n Gram matrix of the POD (3 <= n <= 2048), on the device:
 // all eigenvalues + the k leading eigenvectors, so that `orth` never leaves the GPU for the step
 // that LAPACK dsyevd (19 ms at n = 512 on the host, 13 ms in rocSOLVER) would otherwise dominate.
 //
@@ -11,6 +11,8 @@
 //      bumps a counter; ONE lane polls with s_sleep and a wall-clock bound, the others wait at a
 //      workgroup barrier.  No fences, no dependence on placement; a timeout raises an error word and
 //      every workgroup leaves.
+//      1024 < n <= 2048: the wide route instead (symeig_wide_* below): work copy of G in memory, one launch per
+//      dependency, no workgroup waits for another.
 //   2. symeig_bisect_kernel    eigenvalues of T by Sturm-count multisection: two waves per eigenvalue,
 //      257 sections per pass, 7 passes (257^7 > 2^53).
 //   3. symeig_wy_kernel + symeig_vectors_kernel   one wave per wanted eigenvector: inverse iteration on
@@ -624,6 +626,55 @@ __global__ __launch_bounds__(64) void symeig_vectors_kernel(const VecParams p) {
   // from L2 / HBM (~1-2 us away) while applying one takes ~0.1 us, so the rows are fetched RB at a time, one
   // whole block ahead of the block being applied (lane owns j = lane + 64 q).
   constexpr int PER = NM / 64;
+  if constexpr (NM > 1024) {
+    // NM = 2048: 32 doubles per lane and vector.  z, a block of four being applied and the block fetched ahead would be
+    // 9 x 32 doubles = 576 registers of the 512 a lane has, so this instantiation applies the reflectors two at a time
+    // (z, two rows, and the two rows fetched ahead: 5 x 32 doubles).  The pair's cross product is the first or the last
+    // of the six that symeig_wy_kernel leaves per block of four: v1.v0 and v3.v2.
+    double zr[PER], vc[2][PER], vn[2][PER];
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+      const int j = lane + 64 * q;
+      zr[q] = (j < n) ? z[j] : 0.0;
+    }
+    auto fetch = [&](int k, double (&dst)[PER]) {
+#pragma unroll
+      for (int q = 0; q < PER; ++q) {
+        const int j = lane + 64 * q;
+        dst[q] = (k >= 0 && j > k && j < n) ? p.V[(size_t)k * n + j] : 0.0;
+      }
+    };
+    fetch(n - 3, vc[0]);
+    fetch(n - 4, vc[1]);
+    int pair = 0;
+    for (int k0 = n - 3; k0 >= 0; k0 -= 2, ++pair) {
+      fetch(k0 - 2, vn[0]);
+      fetch(k0 - 3, vn[1]);
+      const double t0 = p.tau[k0], t1 = (k0 >= 1) ? p.tau[k0 - 1] : 0.0;
+      const double c10 = p.C[6 * (pair >> 1) + 5 * (pair & 1)];
+      double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+      for (int q = 0; q < PER; ++q) {
+        a0 = fma(vc[0][q], zr[q], a0);
+        a1 = fma(vc[1][q], zr[q], a1);
+      }
+      a0 = rtw::wave_sum(a0);
+      a1 = rtw::wave_sum(a1);
+      const double s0 = t0 * a0;
+      const double s1 = t1 * (a1 - c10 * s0);
+#pragma unroll
+      for (int q = 0; q < PER; ++q) {
+        zr[q] = fma(-s1, vc[1][q], fma(-s0, vc[0][q], zr[q]));
+        vc[0][q] = vn[0][q];
+        vc[1][q] = vn[1][q];
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+      const int j = lane + 64 * q;
+      if (j < n) z[j] = zr[q];
+    }
+  } else {
   double zr[PER], vc[RBK][PER], vn[RBK][PER];
 #pragma unroll
   for (int q = 0; q < PER; ++q) {
@@ -678,11 +729,243 @@ __global__ __launch_bounds__(64) void symeig_vectors_kernel(const VecParams p) {
     const int j = lane + 64 * q;
     if (j < n) z[j] = zr[q];
   }
+  }
   __syncthreads();
   for (int i = lane; i < n; i += 64) p.W[(size_t)i * p.k + t] = z[i];
 }
 
+
+// ---- wide route: 1024 < n <= 2048 ------------------------------------------------------------------------------------
+// A matrix of this size does not fit the LDS of the chip, and nothing here waits for another workgroup: the work copy of
+// G lives in the composite arena (32 MB at the limit: L2 and Infinity Cache serve it) and EVERY dependency of the
+// Householder reduction is a kernel boundary on the ctx stream.  Two launches per column k (dsytd2 recurrences, the
+// full symmetric matrix is kept, so a row of p = A v is one row's dot product and needs no partial sums between
+// workgroups):
+//   symeig_wide_sweep_kernel    whole chip.  Rows i > k: apply the rank-2 update of step k-1 (A -= v w^T + w v^T) and,
+//                               in the same pass over the row, p_i = A_i . v_k.  One read and one write of the trailing
+//                               matrix per column.
+//   symeig_wide_reflect_kernel  one workgroup.  w_k from p; row k+1 with the update of step k applied in registers; from
+//                               it d, e, tau and the reflector of step k+1 - the sweep of step k+1 then applies the
+//                               update of step k to everything below.
+// Grids and the order of every sum depend on n and k alone - not on the ctx's CU count, its CU mask or where a
+// workgroup lands - and there are no floating-point atomics: the same bits on every stream (the row-sharded POD
+// replicates this reduction on every rank).
+constexpr int NWIDE = 2048;      // largest n of the wide route
+constexpr int WIDE_ROWS = 8;     // rows per workgroup of the sweep kernel; every row and vector buffer is padded by as many
+constexpr int WIDE_T = 256;      // threads per workgroup of both kernels
+constexpr int WIDE_CHUNK = 128;  // columns a wave takes per pass: one 16-byte load per lane and row
+
+struct WideParams {
+  double* A;      // (n + WIDE_ROWS) x lda work copy of G, zero beyond n x n
+  double* V;      // n x n: row k = Householder vector of step k (entries j > k), as TriParams::V
+  double* tau;
+  double* d;
+  double* e;
+  double* vb;     // 2 x (lda + WIDE_ROWS): reflector of step k in buffer k & 1, zero outside (k, n)
+  double* w;      // lda + WIDE_ROWS: w of the latest step, zero outside (k, n)
+  double* pr;     // n + WIDE_ROWS: A v of the current step (not yet scaled by tau)
+  int n, lda;     // lda: n rounded up to WIDE_CHUNK
+  long* counters;
+};
+
+// A = G, zero padded; the vector buffers (contiguous from vb: vb | w | pr) = 0
+__global__ __launch_bounds__(WIDE_T) void symeig_wide_load_kernel(const double* __restrict__ G, const WideParams p, long nvec) {
+  const long idx = (long)blockIdx.x * WIDE_T + threadIdx.x;
+  const long total = (long)(p.n + WIDE_ROWS) * p.lda;
+  if (idx < total) {
+    const int i = (int)(idx / p.lda), j = (int)(idx % p.lda);
+    p.A[idx] = (i < p.n && j < p.n) ? G[(size_t)i * p.n + j] : 0.0;
+  }
+  if (idx < nvec) p.vb[idx] = 0.0;
+}
+
+__global__ __launch_bounds__(WIDE_T) void symeig_wide_sweep_kernel(const WideParams p, int k) {
+  __shared__ double s_acc[WIDE_T / 64][WIDE_ROWS];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, lda = p.lda;
+  const int i0 = k + 1 + WIDE_ROWS * (int)blockIdx.x;   // rows i0 .. i0 + 7 (rows >= n are zero padding and stay zero)
+  const double* __restrict__ vk = p.vb + (size_t)(k & 1) * (lda + WIDE_ROWS);         // v_k
+  const double* __restrict__ vp = p.vb + (size_t)((k + 1) & 1) * (lda + WIDE_ROWS);   // v_{k-1} (zero at k = 0)
+  const double* __restrict__ wp = p.w;                                                // w_{k-1} (zero at k = 0)
+  double vi[WIDE_ROWS], wi[WIDE_ROWS], acc[WIDE_ROWS];
+#pragma unroll
+  for (int r = 0; r < WIDE_ROWS; ++r) {
+    vi[r] = vp[i0 + r];
+    wi[r] = wp[i0 + r];
+    acc[r] = 0.0;
+  }
+  // whole chunks from the one that holds column k + 1: v_{k-1} and w_{k-1} are zero in the columns < k, v_k in the
+  // columns <= k, so the columns a chunk takes along change nothing and add nothing
+  const int nchunk = lda / WIDE_CHUNK;
+#pragma unroll 2
+  for (int c = (k + 1) / WIDE_CHUNK + wid; c < nchunk; c += WIDE_T / 64) {
+    const int j = c * WIDE_CHUNK + 2 * lane;
+    const double2 v2 = *reinterpret_cast<const double2*>(vk + j);
+    const double2 pv = *reinterpret_cast<const double2*>(vp + j);
+    const double2 pw = *reinterpret_cast<const double2*>(wp + j);
+#pragma unroll
+    for (int r = 0; r < WIDE_ROWS; ++r) {
+      double2* row = reinterpret_cast<double2*>(p.A + (size_t)(i0 + r) * lda + j);
+      double2 a = *row;
+      {
+        // products and their sum are rounded one by one: entry (i, j) and entry (j, i) then get the same bits and the
+        // work copy stays exactly symmetric
+#pragma clang fp contract(off)
+        a.x -= vi[r] * pw.x + wi[r] * pv.x;
+        a.y -= vi[r] * pw.y + wi[r] * pv.y;
+      }
+      *row = a;
+      acc[r] = fma(a.x, v2.x, acc[r]);
+      acc[r] = fma(a.y, v2.y, acc[r]);
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < WIDE_ROWS; ++r) {
+    const double t = rtw::wave_sum(acc[r]);
+    if (lane == 0) s_acc[wid][r] = t;
+  }
+  __syncthreads();
+  if (tid < WIDE_ROWS) p.pr[i0 + tid] = ((s_acc[0][tid] + s_acc[1][tid]) + s_acc[2][tid]) + s_acc[3][tid];
+}
+static_assert(WIDE_T == 256, "the sweep kernel adds the partial sums of four waves");
+
+// k = -1: the reflector of step 0 from row 0 of the work copy, nothing to update
+__global__ __launch_bounds__(WIDE_T) void symeig_wide_reflect_kernel(const WideParams p, int k) {
+  constexpr int PER = NWIDE / WIDE_T;
+  __shared__ double s_red[WIDE_T / 64], s_b[3];
+  const int n = p.n, lda = p.lda, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, kk = k + 1;
+  auto block_sum4 = [&](double x) {
+    x = rtw::wave_sum(x);
+    __syncthreads();
+    if (lane == 0) s_red[wid] = x;
+    __syncthreads();
+    return ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];   // same order in every thread
+  };
+  const double* vk = p.vb + (size_t)(k & 1) * (lda + WIDE_ROWS);
+  double* vn = p.vb + (size_t)(kk & 1) * (lda + WIDE_ROWS);
+  const double tau = (k >= 0) ? p.tau[k] : 0.0;
+  double v[PER], w[PER], x[PER];
+#pragma unroll
+  for (int q = 0; q < PER; ++q) {
+    const int j = tid + WIDE_T * q;
+    const bool in = j > k && j < n;
+    v[q] = (k >= 0 && in) ? vk[j] : 0.0;
+    w[q] = (k >= 0 && in) ? tau * p.pr[j] : 0.0;
+    x[q] = in ? p.A[(size_t)kk * lda + j] : 0.0;   // row k + 1 with the updates of the steps < k
+  }
+  if (k >= 0) {
+    double dot = 0.0;
+#pragma unroll
+    for (int q = 0; q < PER; ++q) dot = fma(w[q], v[q], dot);
+    dot = block_sum4(dot);
+    const double alpha2 = -0.5 * tau * dot;
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+      const int j = tid + WIDE_T * q;
+      w[q] = fma(alpha2, v[q], w[q]);
+      if (j == kk) s_b[0] = w[q];   // w_{k+1}; v_{k+1} = 1
+      if (j < lda) p.w[j] = w[q];
+    }
+    __syncthreads();
+    const double w1 = s_b[0];
+#pragma unroll
+    for (int q = 0; q < PER; ++q) x[q] -= w[q] + w1 * v[q];   // row k + 1 after the rank-2 update of step k
+  } else if (tid == 0) {
+    atomicAdd(reinterpret_cast<unsigned long long*>(&p.counters[RT_CNT_EIG_WIDE_FORM]), 1ull);
+  }
+  double part = 0.0;
+#pragma unroll
+  for (int q = 0; q < PER; ++q) {
+    const int j = tid + WIDE_T * q;
+    if (j == kk) s_b[1] = x[q];        // the diagonal entry
+    if (j == kk + 1) s_b[2] = x[q];    // alpha of dlarfg
+    if (j > kk + 1) part = fma(x[q], x[q], part);   // x is 0 beyond the row's end
+  }
+  part = block_sum4(part);
+  const double diag = s_b[1], alpha = s_b[2];
+  if (kk + 2 < n) {
+    double tk, beta, scale;
+    if (part == 0.0) {
+      tk = 0.0; beta = alpha; scale = 0.0;
+    } else {
+      beta = -copysign(sqrt(alpha * alpha + part), alpha);
+      tk = (beta - alpha) / beta;
+      scale = 1.0 / (alpha - beta);
+    }
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+      const int j = tid + WIDE_T * q;
+      const double vq = (j == kk + 1) ? 1.0 : ((j > kk + 1 && j < n) ? x[q] * scale : 0.0);
+      if (j < lda) vn[j] = vq;
+      if (j > kk && j < n) p.V[(size_t)kk * n + j] = vq;
+    }
+    if (tid == 0) {
+      p.tau[kk] = tk;
+      p.d[kk] = diag;
+      p.e[kk] = beta;
+    }
+  } else {
+    // kk = n - 2, the trailing 2 x 2: row n - 1 has the updates of the steps < k, its diagonal entry gets that of step k
+    if (tid == 0) {
+      p.d[kk] = diag;
+      p.e[kk] = alpha;
+      p.e[n - 1] = 0.0;
+    }
+#pragma unroll
+    for (int q = 0; q < PER; ++q)
+      if (tid + WIDE_T * q == n - 1) {
+#pragma clang fp contract(off)
+        p.d[n - 1] = p.A[(size_t)(n - 1) * lda + (n - 1)] - (v[q] * w[q] + w[q] * v[q]);
+      }
+  }
+}
+static_assert(NWIDE % WIDE_CHUNK == 0 && NWIDE % WIDE_T == 0, "the reflector kernel covers a padded row with PER elements per thread");
+
 }  // namespace
+
+// rt_sym_eig_values_part for 1024 < n <= 2048: the wide tridiagonalisation (about 2 n launches, enqueue only) and the
+// multisection at NM = 2048.  Leaves in ctx->eig what symeig_tridiag_kernel's caller leaves there.
+static int sym_eig_values_wide(rt_ctx* ctx, const double* G, int64_t n, int64_t first, int64_t count, double* lam,
+                               int* status) {
+  const int lda = (int)((n + WIDE_CHUNK - 1) / WIDE_CHUNK * WIDE_CHUNK);
+  const size_t nvec = (size_t)3 * (lda + WIDE_ROWS) + (size_t)(n + WIDE_ROWS);
+  // composite arena: V (n*n) | A ((n+8)*lda) | vb (x2), w, pr | tau | d | e | flags
+  size_t off = 0;
+  auto take = [&off](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+  const size_t oV = take(sizeof(double) * n * n), oA = take(sizeof(double) * (size_t)(n + WIDE_ROWS) * lda),
+               oB = take(sizeof(double) * nvec), oT = take(sizeof(double) * n), oD = take(sizeof(double) * n),
+               oE = take(sizeof(double) * n), oF = take(sizeof(int) * (SLOT0 + TW_LARGE));
+  void* base = nullptr;
+  int rc = rt_scratch2(ctx, off, &base);
+  if (rc != RT_OK) return rc;
+  char* b8 = static_cast<char*>(base);
+  WideParams wp;
+  wp.V = reinterpret_cast<double*>(b8 + oV); wp.A = reinterpret_cast<double*>(b8 + oA);
+  wp.vb = reinterpret_cast<double*>(b8 + oB); wp.w = wp.vb + (size_t)2 * (lda + WIDE_ROWS);
+  wp.pr = wp.w + (lda + WIDE_ROWS);
+  wp.tau = reinterpret_cast<double*>(b8 + oT); wp.d = reinterpret_cast<double*>(b8 + oD);
+  wp.e = reinterpret_cast<double*>(b8 + oE);
+  wp.n = (int)n; wp.lda = lda; wp.counters = ctx->dev_counters;
+  int* flags = reinterpret_cast<int*>(b8 + oF);
+  hipStream_t st = ctx->stream;
+  hipLaunchKernelGGL(symeig_init_kernel, dim3(1), dim3(256), 0, st, flags, wp.tau, (int)n);   // flags[3] = 0: no hand-off, no time-out
+  const long cells = (long)(n + WIDE_ROWS) * lda;
+  hipLaunchKernelGGL(symeig_wide_load_kernel, dim3((unsigned)((cells + WIDE_T - 1) / WIDE_T)), dim3(WIDE_T), 0, st, G, wp,
+                     (long)nvec);
+  hipLaunchKernelGGL(symeig_wide_reflect_kernel, dim3(1), dim3(WIDE_T), 0, st, wp, -1);
+  RT_HIP_CHECK(ctx, hipGetLastError());
+  for (int k = 0; k + 2 < (int)n; ++k) {
+    const int rows = (int)n - 1 - k;
+    hipLaunchKernelGGL(symeig_wide_sweep_kernel, dim3((unsigned)((rows + WIDE_ROWS - 1) / WIDE_ROWS)), dim3(WIDE_T), 0, st, wp, k);
+    hipLaunchKernelGGL(symeig_wide_reflect_kernel, dim3(1), dim3(WIDE_T), 0, st, wp, k);
+  }
+  RT_HIP_CHECK(ctx, hipGetLastError());
+  hipLaunchKernelGGL(symeig_bisect_kernel<2048>, dim3((unsigned)((count + 1) / 2)), dim3(256), 0, st, wp.d, wp.e, (int)n,
+                     (int)first, (int)count, lam, flags, status, ctx->dev_counters);
+  RT_HIP_CHECK(ctx, hipGetLastError());
+  ctx->eig.d = wp.d; ctx->eig.e = wp.e; ctx->eig.V = wp.V; ctx->eig.tau = wp.tau; ctx->eig.n = n; ctx->eig.base = base;
+  ctx->eig.gen = ctx->scratch2_gen;
+  return RT_OK;
+}
 
 extern "C" int rt_sym_eig_values(rt_ctx* ctx, const double* G, int64_t n, double* lam, int* status) {
   return rt_sym_eig_values_part(ctx, G, n, 0, n, lam, status);
@@ -692,10 +975,11 @@ extern "C" int rt_sym_eig_values_part(rt_ctx* ctx, const double* G, int64_t n, i
                                       int* status) {
   if (!ctx) return RT_ERR_ARG;
   RT_ARG_CHECK(ctx, G && lam && n >= 3 && first >= 0 && count >= 1 && first + count <= n);
-  if (n > NMAX) {
-    ctx->err = "rt_sym_eig_values: n > 1024 not supported (the matrix must stay resident in the LDS of <= 128 CUs)";
+  if (n > NWIDE) {
+    ctx->err = "rt_sym_eig_values: n > 2048 not supported (the limit of the device eigensolver)";
     return RT_ERR_UNSUPPORTED;
   }
+  if (n > NMAX) return sym_eig_values_wide(ctx, G, n, first, count, lam, status);   // G does not fit the LDS of 128 CUs
   const bool large = n > 512;
   // A ctx confined to few CUs (CU-masked stream of the POD pipeline, "cu_limit") halves the team for n <= 512: 16
   // workgroups hold 32 rows each (147 KB of LDS); a column then costs more mat-vec but the same hand-off.
@@ -807,7 +1091,14 @@ extern "C" int rt_sym_eig_vectors(rt_ctx* ctx, int64_t n, int64_t k, const doubl
   RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&symeig_vectors_kernel<256>), 80 * 1024));
   RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&symeig_vectors_kernel<512>), 80 * 1024));
   RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&symeig_vectors_kernel<1024>), 80 * 1024));
-  if (n > 512) {
+  if (n > 1024) {
+    // 8 arrays of 2048 doubles and the pivot flags: 133 KB of the 160 KB of a CU, this instantiation alone asks for them
+    const size_t vlds = sizeof(double) * (8 * 2048 + 8) + 2048;
+    RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&symeig_vectors_kernel<2048>), 136 * 1024));
+    hipLaunchKernelGGL(symeig_wy_kernel<2048>, dim3((unsigned)nblk), dim3(64), 0, ctx->stream, vp.V, (int)n,
+                       static_cast<double*>(cbuf));
+    hipLaunchKernelGGL(symeig_vectors_kernel<2048>, dim3((unsigned)k), dim3(64), vlds, ctx->stream, vp);
+  } else if (n > 512) {
     const size_t vlds = sizeof(double) * (8 * 1024 + 8) + 1024;
     hipLaunchKernelGGL(symeig_wy_kernel<1024>, dim3((unsigned)nblk), dim3(64), 0, ctx->stream, vp.V, (int)n,
                        static_cast<double*>(cbuf));

@@ -8,7 +8,7 @@ Algorithm (device work through the C ABI, see include/romtime_hip.h):
   pass 1   G = X^T X                        rt_gram        (FP64 MFMA; the only O(N n^2) step)
            [row-sharded X: all-reduce G over RCCL/xGMI here]
            colnorm = sqrt(diag G), G <- D^-1 G D^-1        rt_gram_scale  (normalize=True, pod.py:31-33)
-           G = W L W^T                      rt_sym_eig_values / _vectors (device; host LAPACK for n > 1024)
+           G = W L W^T                      rt_sym_eig_values / _vectors (device; host LAPACK for n > 2048)
            sigma = sqrt(L), energy, truncation -> r
            Q = X (D^-1 W_r S_r^-1)          rt_gemm_nn     (back-projection)
 
@@ -40,7 +40,7 @@ from .pod_rules import DROP_TOLERANCE, LEVEL_RATIO, MAX_LEVELS, RR_GAP, TWO_PASS
 from .pod_rules import energy as _energy
 
 DEVICE_EIG = True      # small eigenproblem on the device (rt_sym_eig_*); False = host LAPACK
-DEVICE_EIG_MAX_N = 1024
+DEVICE_EIG_MAX_N = 2048  # rt_sym_eig_*: LDS-resident tridiagonalisation to 1024, the wide route (one launch per dependency) to 2048
 
 
 # shapes (n, num, normalize) whose last POD could not use the work enqueued ahead of the eigenvalues (pod_device)
@@ -140,7 +140,7 @@ def _inv_or_zero(s):
 
 class _SmallEig:
     """Eigen-decomposition of the n x n Gram matrix: all eigenvalues (host array, descending) at once,
-    leading eigenvectors on request (device, n x k).  3 <= n <= 1024 runs on the device
+    leading eigenvectors on request (device, n x k).  3 <= n <= DEVICE_EIG_MAX_N (2048) runs on the device
     (rt_sym_eig_values / rt_sym_eig_vectors, Rayleigh-Ritz polish on G when the kept eigenvalues are
     not ``pod_rules.separated``); other sizes use host LAPACK.  ``head``: the parsed pod_rules.Head."""
 
