@@ -362,6 +362,22 @@ int rt_sym_eig_values_part(rt_ctx* ctx, const double* G, int64_t n, int64_t firs
  * reflectors kept in the ctx's workspace).  W: n x k row-major, column t pairs with lam[t]. */
 int rt_sym_eig_vectors(rt_ctx* ctx, int64_t n, int64_t k, const double* lam, double* W);
 
+/* Two-sided Jacobi eigen-decomposition of a symmetric n x n DEVICE matrix A (row-major, not modified; its upper triangle
+ * is what counts), 1 <= n <= 2048 (RT_ERR_UNSUPPORTED beyond; null or non-positive arguments RT_ERR_ARG), since version
+ * 360: A = W diag(lam) W^T, lam (n, device) DESCENDING and stable on ties by index, eigenvectors in the columns of W
+ * (n x n row-major, device).  The rotations and the relative stopping rule |a_pq| <= eps sqrt(|a_pp a_qq|) are those of
+ * rt_host_jacobi_eigh below, so small eigenvalues of a graded matrix come out to high relative accuracy; the order is a
+ * round-robin tournament (n - 1 rounds of n / 2 disjoint pairs per sweep, n rounds with one idle index when n is odd),
+ * one launch per round on the ctx stream, the work copies and the rotations in the ctx's composite arena (3 n^2 doubles:
+ * 96 MB at the limit).  The host reads one integer per sweep (it synchronises the stream) and stops after a sweep without
+ * rotations or after max_sweeps: *sweeps_done (HOST int, may be NULL) = sweeps run, the closing one included; status
+ * (DEVICE int) = 0, or 1 when max_sweeps ended the loop (lam and W are written either way).  Grids and every operation
+ * depend on n alone and there is no floating-point atomic: the same bits on a CU-masked stream, on every rank, every time.
+ * rt_last_launch_info: [0] sweeps, [1] rounds per sweep, [2] workgroups of a round.  The second-pass Gram matrix of the
+ * POD (romtime_amd/pod.py, passes=2). */
+int rt_sym_jacobi_eigh(rt_ctx* ctx, const double* A, int64_t n, double* lam, double* W, int max_sweeps, int* sweeps_done,
+                       int* status);
+
 /* ---- host-side small dense step --------------------------------------------------------- */
 /* Cyclic two-sided Jacobi eigen-decomposition of a symmetric PSD n x n HOST matrix A (row-major,
  * destroyed): A = W diag(lam) W^T, lam descending, eigenvectors in the columns of W (row-major).

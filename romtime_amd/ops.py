@@ -430,6 +430,31 @@ def sym_eig_vectors(lam: torch.Tensor, k: int, first: int = 0) -> torch.Tensor:
     return W
 
 
+def sym_jacobi_eigh(G: torch.Tensor, max_sweeps: int = 60):
+    """(lam, W, sweeps) of the symmetric n x n G (n <= 2048, not modified) by two-sided Jacobi on the device: ``lam``
+    descending (device), eigenvectors in the columns of ``W`` (device, n x n), ``sweeps`` the sweeps run (the closing
+    one without rotations included).  Small eigenvalues of a graded matrix come out to high relative accuracy.  Warns
+    if ``max_sweeps`` ended the loop (what the sweeps reached is returned, as the host routine does).  Synchronises the
+    stream once per sweep.  rt_sym_jacobi_eigh."""
+    ctx = Context.current()
+    n = G.shape[0]
+    if G.dtype != torch.float64 or not G.is_cuda or G.dim() != 2 or G.shape != (n, n):
+        raise RomtimeHipError("sym_jacobi_eigh: expected a square float64 CUDA tensor")
+    G = G.contiguous()
+    lam = torch.empty(n, dtype=torch.float64, device=G.device)
+    W = torch.empty((n, n), dtype=torch.float64, device=G.device)
+    status = torch.zeros(1, dtype=torch.int32, device=G.device)
+    sweeps = C.c_int(0)
+    ctx.check(ctx.lib.rt_sym_jacobi_eigh(ctx.handle, _ptr(G), n, _ptr(lam), _ptr(W), int(max_sweeps), C.byref(sweeps),
+                                         _ptr(status)), "rt_sym_jacobi_eigh")
+    if sweeps.value >= max_sweeps and int(status.item()) != 0:
+        import warnings
+
+        warnings.warn(f"romtime_amd: sym_jacobi_eigh stopped at max_sweeps = {max_sweeps} with rotations still applied",
+                      RuntimeWarning)
+    return lam, W, int(sweeps.value)
+
+
 def transpose(src: torch.Tensor) -> torch.Tensor:
     ctx = Context.current()
     src = src.contiguous()

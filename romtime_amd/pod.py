@@ -15,7 +15,10 @@ Algorithm (device work through the C ABI, see include/romtime_hip.h):
   deep spectra (a kept mode with sigma_r/sigma_1 < TWO_PASS_RATIO): deflated levels (_pod_deflated) --
            accept the modes within LEVEL_RATIO of the current largest, X <- X - Q (Q^T X) (rt_gemm_tn/_nn),
            Gram + eigensolve again; every level runs on the device.
-  passes=2 keeps the alternative rotation + host Jacobi route (rt_host_jacobi_eigh).
+  passes=2 keeps the alternative rotation route: Y = X D^-1 W, G2 = Y^T Y, two-sided Jacobi on G2 with the relative
+           stopping rule, on the device (rt_sym_jacobi_eigh, ops.sym_jacobi_eigh; n <= 2048): G2 and its eigenvectors
+           stay there, the eigenvalues are the only transfer before the back-projection Q = Y (W2_r S_r^-1), and VT =
+           (W W2_r)^T is a device product.  Host tensors and n > 2048 take the host routine (rt_host_jacobi_eigh).
 
 One pass reproduces dgesvd's left singular vectors to ~eps (sigma_1/sigma_i)^2.  ``passes=2`` brings that to
 ~eps sigma_1/sigma_i, dgesvd's own accuracy; the deflated levels do so at the top of every level and lose up to
@@ -314,7 +317,7 @@ def pod_device(X: torch.Tensor, num=None, tol=None, normalize=True, passes=None,
     rank's row slab and the Gram matrices are summed over the group.
 
     ``passes``: None = automatic (one Gram pass when every kept mode has sigma_r/sigma_1 >=
-    TWO_PASS_RATIO, otherwise deflated levels), 1 = one pass, 2 = rotation + host Jacobi,
+    TWO_PASS_RATIO, otherwise deflated levels), 1 = one pass, 2 = rotation + Jacobi on the second Gram matrix,
     "deflate" = deflated levels."""
     import time
 
@@ -381,14 +384,29 @@ def pod_device(X: torch.Tensor, num=None, tol=None, normalize=True, passes=None,
     elif passes == 2:
         W = eig.vectors(n)
         Y = ops.gemm_nn(X, (W / colnorm[:, None] if normalize else W).contiguous())
-        G2 = _allreduce(ops.gram(Y), group).cpu().numpy()
-        lam2, W2 = jacobi_eigh(G2)
-        s = pod_rules.sigma(lam2)
-        energy = _energy(s)
-        r = truncation_rank(s, energy, num=num, tol=tol)
-        T2 = W2[:, :r] * _inv_or_zero(s[:r])
-        Q = ops.gemm_nn(Y, ops.to_device(T2, X.device)) if r > 0 else X.new_zeros((X.shape[0], 0))
-        VT = np.ascontiguousarray((W.cpu().numpy() @ W2[:, :r]).T) if want_vt else None
+        G2 = _allreduce(ops.gram(Y), group)
+        if X.is_cuda and n <= DEVICE_EIG_MAX_N:
+            # every rank holds the same G2 and the solver's bits depend on n alone: the eigenvalues are the only transfer
+            lam2_d, W2, _ = ops.sym_jacobi_eigh(G2)
+            s = pod_rules.sigma(lam2_d.cpu().numpy())
+            energy = _energy(s)
+            r = truncation_rank(s, energy, num=num, tol=tol)
+            W2r = W2[:, :r].contiguous()
+            T2 = W2r * ops.to_device(_inv_or_zero(s[:r]), X.device)[None, :]
+            Q = ops.gemm_nn(Y, T2) if r > 0 else X.new_zeros((X.shape[0], 0))
+            if want_vt:
+                VT = np.ascontiguousarray(ops.gemm_nn(W, W2r).cpu().numpy().T) if r > 0 else np.zeros((0, n))
+            else:
+                VT = None
+        else:   # host tensors (the stand-ins of the CPU tests) and n > 2048: the host routine, as before
+            G2 = G2.cpu().numpy()
+            lam2, W2 = jacobi_eigh(G2)
+            s = pod_rules.sigma(lam2)
+            energy = _energy(s)
+            r = truncation_rank(s, energy, num=num, tol=tol)
+            T2 = W2[:, :r] * _inv_or_zero(s[:r])
+            Q = ops.gemm_nn(Y, ops.to_device(T2, X.device)) if r > 0 else X.new_zeros((X.shape[0], 0))
+            VT = np.ascontiguousarray((W.cpu().numpy() @ W2[:, :r]).T) if want_vt else None
     elif passes == "deflate":
         Q, s, energy, r, VT, levels = _pod_deflated(X, eig, colnorm, normalize, num, tol, group, want_vt)
     else:
