@@ -17,9 +17,13 @@
 //      257 sections per pass, 7 passes (257^7 > 2^53).
 //   3. symeig_wy_kernel + symeig_vectors_kernel   one wave per wanted eigenvector: inverse iteration on
 //      T - lambda I (pivoted tridiagonal LU, as dstein) in LDS, then the reflectors applied in reverse,
-//      four per reduction round.
+//      four per reduction round (two at NM = 2048).
+// Every kernel templated on NM is instantiated for a few size classes; size_class() is the one place that maps n to
+// its class.
 // The caller (pod.py) adds a k x k Rayleigh-Ritz step on G when kept eigenvalues are clustered, which also
 // cross-checks the Ritz values against the multisection eigenvalues; a mismatch raises (nothing silent).
+#include <type_traits>
+
 #include "common.h"
 #include "wave_ops.h"
 
@@ -31,7 +35,7 @@ constexpr int TW_LARGE = 128;  // 512 < n <= 1024: 8 rows of 1024 per workgroup
 constexpr int LPR = 64;     // lanes per matrix row in the mat-vec / rank-2 update (TT / LPR rows per pass)
 constexpr int TT = 1024;    // threads per workgroup
 static_assert(LPR == 64, "row reductions use the whole-wave DPP sum");
-constexpr int NMAX = 1024;     // largest supported n; the kernels are instantiated for 128, 256, 512 and 1024
+constexpr int NMAX = 1024;     // largest n of the cooperative tridiagonalisation (G in the LDS of the chip); above it: the wide route
 // inverse iterations per eigenvector: the shifts are eigenvalues to full precision, so the first solve already
 // amplifies the wanted direction by ~1/eps and the second removes what is left of the start vector (dstein also
 // stops after two or three); the caller's Rayleigh-Ritz step cross-checks the result
@@ -44,10 +48,11 @@ struct TriParams {
   double* tau;       // n
   double* d;         // n
   double* e;         // n
-  int* flags;        // [3] = error, [4] = worker tickets of the one-XCD form, [8 .. 8 + tw) = XCC id of each workgroup, [SLOT0 .. SLOT0 + tw) = arrival slots
+  int* flags;        // SLOT0 + TW_LARGE words: [3] = error, [4] = worker tickets of the one-XCD form, [8 .. 8 + tw) = XCC id + 1
+                     // of each workgroup, [SLOT0 .. SLOT0 + tw) = arrival slots
   int n;
   int tw;            // cooperating workgroups
-  int local;         // 1: ONE workgroup holds the whole matrix (n <= 128): p and the next row never leave its LDS
+  int local;         // 1: ONE workgroup holds the whole matrix (the host takes this form for n <= 64): p and the next row never leave its LDS
   int spread;        // 1: launched as 8 tw blocks, only the blocks with blockIdx % 8 == xcd work (they share an XCD)
   int xcd;
   long* counters;    // rt_ctx::dev_counters: which hand-off form ran, and time-outs (rt_ctx_get_counter)
@@ -98,15 +103,21 @@ __device__ __forceinline__ bool poll_slots(int* slots, int TW, int want, int* er
   }
 }
 
-__device__ __forceinline__ double block_sum(double x, double* s_red) {
-  x = rtw::wave_sum(x);
-  const int wid = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_red[wid] = x;
-  __syncthreads();
-  double t = 0.0;
-  for (int w = 0; w < TT / 64; ++w) t += s_red[w];  // same order in every thread
-  return t;
+// Coefficients of the Householder reflector of a row (LAPACK dlarfg): alpha = its first entry, part = the sum of the
+// squares of the others -> v = (1, scale * others), and H = I - tau v v^T maps the row to (beta, 0, ...).
+struct Dlarfg {
+  double tau, beta, scale;
+};
+__device__ __forceinline__ Dlarfg dlarfg(double alpha, double part) {
+  double tau, beta, scale;
+  if (part == 0.0) {
+    tau = 0.0; beta = alpha; scale = 0.0;
+  } else {
+    beta = -copysign(sqrt(alpha * alpha + part), alpha);
+    tau = (beta - alpha) / beta;
+    scale = 1.0 / (alpha - beta);
+  }
+  return {tau, beta, scale};
 }
 
 // One inter-workgroup hand-off per column: together with its slice of p = tau A v, the owner of row
@@ -161,7 +172,7 @@ __global__ __launch_bounds__(TT) void symeig_tridiag_kernel(const TriParams p) {
   double* L0 = p.P + (size_t)3 * n;
   __shared__ int s_one;
   if (local) {
-    // Round 3: a Gram matrix of up to 128 columns fits ONE workgroup's LDS.  A column then needs no hand-off at all -
+    // One-workgroup form: a Gram matrix of up to 128 columns fits ONE workgroup's LDS.  A column then needs no hand-off at all -
     // no payload stores to drain, no arrival slot, no poll, no payload loads: each of those is a memory round trip of
     // 0.5-0.7 us that the cooperative form pays even when the "team" is a single workgroup (3.3 us per column at n = 64
     // whatever the team size).  p goes through LDS (sP), the next row is read where it lies.
@@ -215,15 +226,8 @@ __global__ __launch_bounds__(TT) void symeig_tridiag_kernel(const TriParams p) {
     for (int q = 0; q < PER; ++q)
       if (q > 0 || lane > off) part = fma(x[q], x[q], part);  // x is 0 beyond the row's end
     part = rtw::wave_sum(part);
-    const double alpha = rtw::read_lane(x[0], off);
-    double tau, beta, scale;
-    if (part == 0.0) {
-      tau = 0.0; beta = alpha; scale = 0.0;
-    } else {
-      beta = -copysign(sqrt(alpha * alpha + part), alpha);
-      tau = (beta - alpha) / beta;
-      scale = 1.0 / (alpha - beta);
-    }
+    const Dlarfg h = dlarfg(rtw::read_lane(x[0], off), part);
+    const double tau = h.tau, beta = h.beta, scale = h.scale;
     const bool owner = (wg == kk % TW);
     double* svk = svb + (size_t)(kk & 1) * n;
 #pragma unroll
@@ -299,12 +303,9 @@ __global__ __launch_bounds__(TT) void symeig_tridiag_kernel(const TriParams p) {
           double acc = 0.0;
           for (int j = k + 1 + tx; j < n; j += LPR) acc = fma(row[j], sv[j], acc);
           acc = rtw::wave_sum(acc);
-          if (tx == 0) {
-            if (local) sP[gi] = tau * acc;
-            else st_xcd(&Pk[gi], tau * acc, one_xcd);
-          }
+          if (tx == 0) st_xcd(&Pk[gi], tau * acc, one_xcd);
         }
-        if (gi == k + 1 && !local)
+        if (gi == k + 1)
           for (int j = k + 1 + tx; j < n; j += LPR) st_xcd(&Lk[j], row[j], one_xcd);
       }
     }
@@ -402,18 +403,6 @@ __global__ __launch_bounds__(TT) void symeig_tridiag_kernel(const TriParams p) {
 __device__ __forceinline__ double fast_rcp(double q) {
   const double r = __builtin_amdgcn_rcp(q);
   return fma(fma(-q, r, 1.0), r, r);
-}
-
-__device__ __forceinline__ int sturm_count(const double* d, const double* e2, int n, double x, double pivmin) {
-  double q = d[0] - x;
-  if (fabs(q) < pivmin) q = -pivmin;
-  int c = (q < 0.0);
-  for (int i = 1; i < n; ++i) {
-    q = fma(-e2[i - 1], fast_rcp(q), d[i] - x);
-    if (fabs(q) < pivmin) q = -pivmin;
-    c += (q < 0.0);
-  }
-  return c;
 }
 
 __global__ void symeig_init_kernel(int* flags, double* tau, int n) {
@@ -626,56 +615,12 @@ __global__ __launch_bounds__(64) void symeig_vectors_kernel(const VecParams p) {
   // from L2 / HBM (~1-2 us away) while applying one takes ~0.1 us, so the rows are fetched RB at a time, one
   // whole block ahead of the block being applied (lane owns j = lane + 64 q).
   constexpr int PER = NM / 64;
-  if constexpr (NM > 1024) {
-    // NM = 2048: 32 doubles per lane and vector.  z, a block of four being applied and the block fetched ahead would be
-    // 9 x 32 doubles = 576 registers of the 512 a lane has, so this instantiation applies the reflectors two at a time
-    // (z, two rows, and the two rows fetched ahead: 5 x 32 doubles).  The pair's cross product is the first or the last
-    // of the six that symeig_wy_kernel leaves per block of four: v1.v0 and v3.v2.
-    double zr[PER], vc[2][PER], vn[2][PER];
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int j = lane + 64 * q;
-      zr[q] = (j < n) ? z[j] : 0.0;
-    }
-    auto fetch = [&](int k, double (&dst)[PER]) {
-#pragma unroll
-      for (int q = 0; q < PER; ++q) {
-        const int j = lane + 64 * q;
-        dst[q] = (k >= 0 && j > k && j < n) ? p.V[(size_t)k * n + j] : 0.0;
-      }
-    };
-    fetch(n - 3, vc[0]);
-    fetch(n - 4, vc[1]);
-    int pair = 0;
-    for (int k0 = n - 3; k0 >= 0; k0 -= 2, ++pair) {
-      fetch(k0 - 2, vn[0]);
-      fetch(k0 - 3, vn[1]);
-      const double t0 = p.tau[k0], t1 = (k0 >= 1) ? p.tau[k0 - 1] : 0.0;
-      const double c10 = p.C[6 * (pair >> 1) + 5 * (pair & 1)];
-      double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-      for (int q = 0; q < PER; ++q) {
-        a0 = fma(vc[0][q], zr[q], a0);
-        a1 = fma(vc[1][q], zr[q], a1);
-      }
-      a0 = rtw::wave_sum(a0);
-      a1 = rtw::wave_sum(a1);
-      const double s0 = t0 * a0;
-      const double s1 = t1 * (a1 - c10 * s0);
-#pragma unroll
-      for (int q = 0; q < PER; ++q) {
-        zr[q] = fma(-s1, vc[1][q], fma(-s0, vc[0][q], zr[q]));
-        vc[0][q] = vn[0][q];
-        vc[1][q] = vn[1][q];
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int j = lane + 64 * q;
-      if (j < n) z[j] = zr[q];
-    }
-  } else {
-  double zr[PER], vc[RBK][PER], vn[RBK][PER];
+  // NM = 2048: 32 doubles per lane and vector.  z, a block of four being applied and the block fetched ahead would be
+  // 9 x 32 doubles = 576 registers of the 512 a lane has, so this instantiation applies the reflectors two at a time
+  // (z, two rows, and the two rows fetched ahead: 5 x 32 doubles).  The pair's cross product is the first or the last
+  // of the six that symeig_wy_kernel leaves per block of four: v1.v0 and v3.v2.
+  constexpr int RB = (NM > 1024) ? 2 : RBK;
+  double zr[PER], vc[RB][PER], vn[RB][PER];
 #pragma unroll
   for (int q = 0; q < PER; ++q) {
     const int j = lane + 64 * q;
@@ -689,38 +634,49 @@ __global__ __launch_bounds__(64) void symeig_vectors_kernel(const VecParams p) {
     }
   };
 #pragma unroll
-  for (int u = 0; u < RBK; ++u) fetch(n - 3 - u, vc[u]);
+  for (int u = 0; u < RB; ++u) fetch(n - 3 - u, vc[u]);
   int blk = 0;
-  for (int k0 = n - 3; k0 >= 0; k0 -= RBK, ++blk) {
+  for (int k0 = n - 3; k0 >= 0; k0 -= RB, ++blk) {
 #pragma unroll
-    for (int u = 0; u < RBK; ++u) fetch(k0 - RBK - u, vn[u]);
-    double tk[RBK], cc[6];
+    for (int u = 0; u < RB; ++u) fetch(k0 - RB - u, vn[u]);
+    double tk[RB], cc[RB * (RB - 1) / 2];   // cc[u (u - 1) / 2 + w] = v_u . v_w, w < u
 #pragma unroll
-    for (int u = 0; u < RBK; ++u) tk[u] = (k0 - u >= 0) ? p.tau[k0 - u] : 0.0;
+    for (int u = 0; u < RB; ++u) tk[u] = (k0 - u >= 0) ? p.tau[k0 - u] : 0.0;
+    if constexpr (RB == RBK) {
 #pragma unroll
-    for (int q = 0; q < 6; ++q) cc[q] = p.C[6 * blk + q];
-    // the four reflectors k0, k0-1, k0-2, k0-3 at once: a_u = v_u . z for the incoming z (four independent
-    // reductions), then s_u = tau_u (a_u - sum_{w<u} (v_u . v_w) s_w) and z -= sum_u s_u v_u.  One reduction round
-    // on the serial chain per block instead of one per reflector.
-    double a[RBK];
+      for (int q = 0; q < 6; ++q) cc[q] = p.C[6 * blk + q];
+    } else {
+      cc[0] = p.C[6 * (blk >> 1) + 5 * (blk & 1)];
+    }
+    // the RB reflectors k0, k0-1, ... at once: a_u = v_u . z for the incoming z (RB independent reductions), then
+    // s_u = tau_u (a_u - sum_{w<u} (v_u . v_w) s_w) and z -= sum_u s_u v_u.  One reduction round on the serial chain
+    // per block instead of one per reflector.
+    double a[RB], s[RB];
 #pragma unroll
-    for (int u = 0; u < RBK; ++u) {
+    for (int u = 0; u < RB; ++u) {
       double dot = 0.0;
 #pragma unroll
       for (int q = 0; q < PER; ++q) dot = fma(vc[u][q], zr[q], dot);
       a[u] = dot;
     }
 #pragma unroll
-    for (int u = 0; u < RBK; ++u) a[u] = rtw::wave_sum(a[u]);
-    const double s0 = tk[0] * a[0];
-    const double s1 = tk[1] * (a[1] - cc[0] * s0);
-    const double s2 = tk[2] * (a[2] - cc[1] * s0 - cc[2] * s1);
-    const double s3 = tk[3] * (a[3] - cc[3] * s0 - cc[4] * s1 - cc[5] * s2);
+    for (int u = 0; u < RB; ++u) a[u] = rtw::wave_sum(a[u]);
 #pragma unroll
-    for (int q = 0; q < PER; ++q)
-      zr[q] = fma(-s3, vc[3][q], fma(-s2, vc[2][q], fma(-s1, vc[1][q], fma(-s0, vc[0][q], zr[q]))));
+    for (int u = 0; u < RB; ++u) {
+      double r = a[u];
 #pragma unroll
-    for (int u = 0; u < RBK; ++u)
+      for (int w = 0; w < u; ++w) r -= cc[u * (u - 1) / 2 + w] * s[w];
+      s[u] = tk[u] * r;
+    }
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+      double zq = zr[q];
+#pragma unroll
+      for (int u = 0; u < RB; ++u) zq = fma(-s[u], vc[u][q], zq);
+      zr[q] = zq;
+    }
+#pragma unroll
+    for (int u = 0; u < RB; ++u)
 #pragma unroll
       for (int q = 0; q < PER; ++q) vc[u][q] = vn[u][q];
   }
@@ -728,7 +684,6 @@ __global__ __launch_bounds__(64) void symeig_vectors_kernel(const VecParams p) {
   for (int q = 0; q < PER; ++q) {
     const int j = lane + 64 * q;
     if (j < n) z[j] = zr[q];
-  }
   }
   __syncthreads();
   for (int i = lane; i < n; i += 64) p.W[(size_t)i * p.k + t] = z[i];
@@ -883,14 +838,8 @@ __global__ __launch_bounds__(WIDE_T) void symeig_wide_reflect_kernel(const WideP
   part = block_sum4(part);
   const double diag = s_b[1], alpha = s_b[2];
   if (kk + 2 < n) {
-    double tk, beta, scale;
-    if (part == 0.0) {
-      tk = 0.0; beta = alpha; scale = 0.0;
-    } else {
-      beta = -copysign(sqrt(alpha * alpha + part), alpha);
-      tk = (beta - alpha) / beta;
-      scale = 1.0 / (alpha - beta);
-    }
+    const Dlarfg h = dlarfg(alpha, part);
+    const double tk = h.tau, beta = h.beta, scale = h.scale;
 #pragma unroll
     for (int q = 0; q < PER; ++q) {
       const int j = tid + WIDE_T * q;
@@ -920,6 +869,50 @@ __global__ __launch_bounds__(WIDE_T) void symeig_wide_reflect_kernel(const WideP
 }
 static_assert(NWIDE % WIDE_CHUNK == 0 && NWIDE % WIDE_T == 0, "the reflector kernel covers a padded row with PER elements per thread");
 
+// The size table: a kernel templated on NM serves every n <= NM and is instantiated for the powers of two from LO to
+// HI; f is called with std::integral_constant<int, NM> for the smallest of them that holds n (HI: the caller has
+// checked n <= HI).
+template <int LO, int HI, class F>
+int size_class(int64_t n, F&& f) {
+  if constexpr (LO < HI)
+    if (n > LO) return size_class<2 * LO, HI>(n, f);
+  return f(std::integral_constant<int, LO>{});
+}
+
+// What a tridiagonalisation leaves in the composite arena: V (n*n) | a block of the route's own | tau | d | e | flags,
+// each rounded up to 256 bytes.  publish() hands it to rt_sym_eig_vectors once everything is enqueued.
+struct EigArena {
+  void* base;
+  double *V, *own, *tau, *d, *e;
+  int* flags;
+  int carve(rt_ctx* ctx, int64_t n, size_t own_bytes) {
+    size_t off = 0;
+    auto take = [&off](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+    const size_t oV = take(sizeof(double) * n * n), oO = take(own_bytes), oT = take(sizeof(double) * n),
+                 oD = take(sizeof(double) * n), oE = take(sizeof(double) * n), oF = take(sizeof(int) * (SLOT0 + TW_LARGE));
+    RT_TRY(rt_scratch2(ctx, off, &base));
+    char* b8 = static_cast<char*>(base);
+    V = reinterpret_cast<double*>(b8 + oV); own = reinterpret_cast<double*>(b8 + oO);
+    tau = reinterpret_cast<double*>(b8 + oT); d = reinterpret_cast<double*>(b8 + oD);
+    e = reinterpret_cast<double*>(b8 + oE); flags = reinterpret_cast<int*>(b8 + oF);
+    return RT_OK;
+  }
+  void publish(rt_ctx* ctx, int64_t n) const {
+    ctx->eig.d = d; ctx->eig.e = e; ctx->eig.V = V; ctx->eig.tau = tau; ctx->eig.n = n; ctx->eig.base = base;
+    ctx->eig.gen = ctx->scratch2_gen;
+  }
+};
+
+// the multisection on the tridiagonal matrix in the arena (n <= 512 runs the 512 instantiation)
+int launch_bisect(rt_ctx* ctx, const EigArena& a, int64_t n, int64_t first, int64_t count, double* lam, int* status) {
+  return size_class<512, NWIDE>(n, [&](auto nm) {
+    hipLaunchKernelGGL(symeig_bisect_kernel<decltype(nm)::value>, dim3((unsigned)((count + 1) / 2)), dim3(256), 0, ctx->stream, a.d,
+                       a.e, (int)n, (int)first, (int)count, lam, a.flags, status, ctx->dev_counters);
+    RT_HIP_CHECK(ctx, hipGetLastError());
+    return (int)RT_OK;
+  });
+}
+
 }  // namespace
 
 // rt_sym_eig_values_part for 1024 < n <= 2048: the wide tridiagonalisation (about 2 n launches, enqueue only) and the
@@ -928,27 +921,19 @@ static int sym_eig_values_wide(rt_ctx* ctx, const double* G, int64_t n, int64_t 
                                int* status) {
   const int lda = (int)((n + WIDE_CHUNK - 1) / WIDE_CHUNK * WIDE_CHUNK);
   const size_t nvec = (size_t)3 * (lda + WIDE_ROWS) + (size_t)(n + WIDE_ROWS);
-  // composite arena: V (n*n) | A ((n+8)*lda) | vb (x2), w, pr | tau | d | e | flags
-  size_t off = 0;
-  auto take = [&off](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-  const size_t oV = take(sizeof(double) * n * n), oA = take(sizeof(double) * (size_t)(n + WIDE_ROWS) * lda),
-               oB = take(sizeof(double) * nvec), oT = take(sizeof(double) * n), oD = take(sizeof(double) * n),
-               oE = take(sizeof(double) * n), oF = take(sizeof(int) * (SLOT0 + TW_LARGE));
-  void* base = nullptr;
-  int rc = rt_scratch2(ctx, off, &base);
-  if (rc != RT_OK) return rc;
-  char* b8 = static_cast<char*>(base);
+  // the route's block of the arena: A ((n+8)*lda, a whole number of 256-byte units) | vb (x2), w, pr
+  static_assert(sizeof(double) * WIDE_CHUNK % 256 == 0, "the vector buffers start on a 256-byte boundary");
+  const size_t cells = (size_t)(n + WIDE_ROWS) * lda;
+  EigArena ar;
+  RT_TRY(ar.carve(ctx, n, sizeof(double) * (cells + nvec)));
   WideParams wp;
-  wp.V = reinterpret_cast<double*>(b8 + oV); wp.A = reinterpret_cast<double*>(b8 + oA);
-  wp.vb = reinterpret_cast<double*>(b8 + oB); wp.w = wp.vb + (size_t)2 * (lda + WIDE_ROWS);
+  wp.V = ar.V; wp.A = ar.own;
+  wp.vb = wp.A + cells; wp.w = wp.vb + (size_t)2 * (lda + WIDE_ROWS);
   wp.pr = wp.w + (lda + WIDE_ROWS);
-  wp.tau = reinterpret_cast<double*>(b8 + oT); wp.d = reinterpret_cast<double*>(b8 + oD);
-  wp.e = reinterpret_cast<double*>(b8 + oE);
+  wp.tau = ar.tau; wp.d = ar.d; wp.e = ar.e;
   wp.n = (int)n; wp.lda = lda; wp.counters = ctx->dev_counters;
-  int* flags = reinterpret_cast<int*>(b8 + oF);
   hipStream_t st = ctx->stream;
-  hipLaunchKernelGGL(symeig_init_kernel, dim3(1), dim3(256), 0, st, flags, wp.tau, (int)n);   // flags[3] = 0: no hand-off, no time-out
-  const long cells = (long)(n + WIDE_ROWS) * lda;
+  hipLaunchKernelGGL(symeig_init_kernel, dim3(1), dim3(256), 0, st, ar.flags, wp.tau, (int)n);   // flags[3] = 0: no hand-off, no time-out
   hipLaunchKernelGGL(symeig_wide_load_kernel, dim3((unsigned)((cells + WIDE_T - 1) / WIDE_T)), dim3(WIDE_T), 0, st, G, wp,
                      (long)nvec);
   hipLaunchKernelGGL(symeig_wide_reflect_kernel, dim3(1), dim3(WIDE_T), 0, st, wp, -1);
@@ -959,11 +944,8 @@ static int sym_eig_values_wide(rt_ctx* ctx, const double* G, int64_t n, int64_t 
     hipLaunchKernelGGL(symeig_wide_reflect_kernel, dim3(1), dim3(WIDE_T), 0, st, wp, k);
   }
   RT_HIP_CHECK(ctx, hipGetLastError());
-  hipLaunchKernelGGL(symeig_bisect_kernel<2048>, dim3((unsigned)((count + 1) / 2)), dim3(256), 0, st, wp.d, wp.e, (int)n,
-                     (int)first, (int)count, lam, flags, status, ctx->dev_counters);
-  RT_HIP_CHECK(ctx, hipGetLastError());
-  ctx->eig.d = wp.d; ctx->eig.e = wp.e; ctx->eig.V = wp.V; ctx->eig.tau = wp.tau; ctx->eig.n = n; ctx->eig.base = base;
-  ctx->eig.gen = ctx->scratch2_gen;
+  RT_TRY(launch_bisect(ctx, ar, n, first, count, lam, status));
+  ar.publish(ctx, n);
   return RT_OK;
 }
 
@@ -995,15 +977,8 @@ extern "C" int rt_sym_eig_values_part(rt_ctx* ctx, const double* G, int64_t n, i
     ctx->err = "rt_sym_eig_values: not enough compute units for the cooperative tridiagonalisation";
     return RT_ERR_UNSUPPORTED;
   }
-  // composite arena: V (n*n) | P (2n) | tau | d | e | flags
-  size_t off = 0;
-  auto take = [&off](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-  const size_t oV = take(sizeof(double) * n * n), oP = take(sizeof(double) * 4 * n), oT = take(sizeof(double) * n),
-               oD = take(sizeof(double) * n), oE = take(sizeof(double) * n), oF = take(sizeof(int) * (SLOT0 + TW_LARGE));
-  void* base = nullptr;
-  int rc = rt_scratch2(ctx, off, &base);
-  if (rc != RT_OK) return rc;
-  char* b8 = static_cast<char*>(base);
+  EigArena ar;
+  RT_TRY(ar.carve(ctx, n, sizeof(double) * 4 * n));   // the route's block of the arena: P (4n)
   TriParams tp;
   tp.G = G; tp.n = (int)n; tp.tw = tw;
   // n <= 512: launch 16 x 32 blocks, of which the first 32 that find themselves on XCD eig_xcd work, so the 32
@@ -1012,60 +987,34 @@ extern "C" int rt_sym_eig_values_part(rt_ctx* ctx, const double* G, int64_t n, i
   tp.spread = (!large && !local && ctx->eig_one_xcd && ctx->num_cus / 8 >= tw) ? 1 : 0;  // a CU per worker
   tp.local = local ? 1 : 0;
   tp.xcd = ctx->eig_xcd & 7;
-  tp.V = reinterpret_cast<double*>(b8 + oV); tp.P = reinterpret_cast<double*>(b8 + oP);
-  tp.tau = reinterpret_cast<double*>(b8 + oT); tp.d = reinterpret_cast<double*>(b8 + oD);
-  tp.e = reinterpret_cast<double*>(b8 + oE); tp.flags = reinterpret_cast<int*>(b8 + oF);
+  tp.V = ar.V; tp.P = ar.own; tp.tau = ar.tau; tp.d = ar.d; tp.e = ar.e; tp.flags = ar.flags;
   tp.counters = ctx->dev_counters;
   hipStream_t st = ctx->stream;
   hipLaunchKernelGGL(symeig_init_kernel, dim3(1), dim3(256), 0, st, tp.flags, tp.tau, (int)n);
 
   const int RB = (int)((n + tw - 1) / tw);
   const size_t lds = sizeof(double) * ((size_t)RB * (local ? n + 2 : n) + 5 * n + 16);  // A slab | v (x2) | w | row | p (local form)
-  // n <= 256 has instantiations of its own (round 3): wave 0's register work per column - reflector, w, the updated row:
-  // NM / 64 elements per lane - and the eigenvector kernel's back-transformation halve against the 512 ones
-  const bool tiny = n <= 256, tinier = n <= 128;
-  RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&symeig_tridiag_kernel<128>), 150 * 1024));
-  RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&symeig_tridiag_kernel<256>), 150 * 1024));
-  RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&symeig_tridiag_kernel<512>), 150 * 1024));
-  RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&symeig_tridiag_kernel<1024>), 150 * 1024));
-  {
+  // n <= 128 and n <= 256 have instantiations of their own: wave 0's register work per column - reflector, w, the updated
+  // row: NM / 64 elements per lane - and the eigenvector kernel's back-transformation halve against the 512 ones
+  const auto tridiag = [&](auto nm) -> int {
+    const auto kernel = &symeig_tridiag_kernel<decltype(nm)::value>;
+    RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(kernel), 150 * 1024));
     // The tw workers spin on each other: all of them must be resident at once.  Ask the runtime how many of these
     // workgroups a CU holds (1: the slab takes most of its LDS) and refuse up front what the device cannot hold,
     // instead of finding out through the hand-off's wall-clock bound.
     int per_cu = 0;
-    if (large)
-      RT_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, symeig_tridiag_kernel<1024>, TT, lds));
-    else if (tinier)
-      RT_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, symeig_tridiag_kernel<128>, TT, lds));
-    else if (tiny)
-      RT_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, symeig_tridiag_kernel<256>, TT, lds));
-    else
-      RT_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, symeig_tridiag_kernel<512>, TT, lds));
+    RT_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, TT, lds));
     if ((long)per_cu * ctx->num_cus < tw) {
       ctx->err = "rt_sym_eig_values: the device cannot keep all cooperating workgroups resident";
       return RT_ERR_UNSUPPORTED;
     }
-  }
-  const dim3 bgrid((unsigned)((count + 1) / 2));
-  if (large) {
-    hipLaunchKernelGGL(symeig_tridiag_kernel<1024>, dim3(tw), dim3(TT), lds, st, tp);
+    hipLaunchKernelGGL(kernel, dim3(tp.spread ? 16 * tw : tw), dim3(TT), lds, st, tp);
     RT_HIP_CHECK(ctx, hipGetLastError());
-    hipLaunchKernelGGL(symeig_bisect_kernel<1024>, bgrid, dim3(256), 0, st, tp.d, tp.e, (int)n, (int)first, (int)count,
-                       lam, tp.flags, status, ctx->dev_counters);
-  } else {
-    if (tinier)
-      hipLaunchKernelGGL(symeig_tridiag_kernel<128>, dim3(tp.spread ? 16 * tw : tw), dim3(TT), lds, st, tp);
-    else if (tiny)
-      hipLaunchKernelGGL(symeig_tridiag_kernel<256>, dim3(tp.spread ? 16 * tw : tw), dim3(TT), lds, st, tp);
-    else
-      hipLaunchKernelGGL(symeig_tridiag_kernel<512>, dim3(tp.spread ? 16 * tw : tw), dim3(TT), lds, st, tp);
-    RT_HIP_CHECK(ctx, hipGetLastError());
-    hipLaunchKernelGGL(symeig_bisect_kernel<512>, bgrid, dim3(256), 0, st, tp.d, tp.e, (int)n, (int)first, (int)count,
-                       lam, tp.flags, status, ctx->dev_counters);
-  }
-  RT_HIP_CHECK(ctx, hipGetLastError());
-  ctx->eig.d = tp.d; ctx->eig.e = tp.e; ctx->eig.V = tp.V; ctx->eig.tau = tp.tau; ctx->eig.n = n; ctx->eig.base = base;
-  ctx->eig.gen = ctx->scratch2_gen;
+    return RT_OK;
+  };
+  RT_TRY((size_class<128, NMAX>(n, tridiag)));
+  RT_TRY(launch_bisect(ctx, ar, n, first, count, lam, status));
+  ar.publish(ctx, n);
   return RT_OK;
 }
 
@@ -1087,38 +1036,16 @@ extern "C" int rt_sym_eig_vectors(rt_ctx* ctx, int64_t n, int64_t k, const doubl
   int rc = rt_scratch(ctx, sizeof(double) * 6 * (size_t)nblk, &cbuf);  // leaf arena: free between the two calls
   if (rc != RT_OK) return rc;
   vp.C = static_cast<const double*>(cbuf);
-  RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&symeig_vectors_kernel<128>), 80 * 1024));
-  RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&symeig_vectors_kernel<256>), 80 * 1024));
-  RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&symeig_vectors_kernel<512>), 80 * 1024));
-  RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&symeig_vectors_kernel<1024>), 80 * 1024));
-  if (n > 1024) {
-    // 8 arrays of 2048 doubles and the pivot flags: 133 KB of the 160 KB of a CU, this instantiation alone asks for them
-    const size_t vlds = sizeof(double) * (8 * 2048 + 8) + 2048;
-    RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&symeig_vectors_kernel<2048>), 136 * 1024));
-    hipLaunchKernelGGL(symeig_wy_kernel<2048>, dim3((unsigned)nblk), dim3(64), 0, ctx->stream, vp.V, (int)n,
+  return size_class<128, NWIDE>(n, [&](auto nm) -> int {
+    constexpr int NM = decltype(nm)::value;
+    // 8 arrays of NM (+1) doubles and the pivot flags.  At NM = 2048 that is 133 KB of the 160 KB of a CU: that
+    // instantiation alone asks for them
+    const size_t vlds = sizeof(double) * (8 * NM + 8) + NM;
+    RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&symeig_vectors_kernel<NM>), (NM > 1024 ? 136 : 80) * 1024));
+    hipLaunchKernelGGL(symeig_wy_kernel<NM>, dim3((unsigned)nblk), dim3(64), 0, ctx->stream, vp.V, (int)n,
                        static_cast<double*>(cbuf));
-    hipLaunchKernelGGL(symeig_vectors_kernel<2048>, dim3((unsigned)k), dim3(64), vlds, ctx->stream, vp);
-  } else if (n > 512) {
-    const size_t vlds = sizeof(double) * (8 * 1024 + 8) + 1024;
-    hipLaunchKernelGGL(symeig_wy_kernel<1024>, dim3((unsigned)nblk), dim3(64), 0, ctx->stream, vp.V, (int)n,
-                       static_cast<double*>(cbuf));
-    hipLaunchKernelGGL(symeig_vectors_kernel<1024>, dim3((unsigned)k), dim3(64), vlds, ctx->stream, vp);
-  } else if (n <= 128) {
-    const size_t vlds = sizeof(double) * (8 * 128 + 8) + 128;
-    hipLaunchKernelGGL(symeig_wy_kernel<128>, dim3((unsigned)nblk), dim3(64), 0, ctx->stream, vp.V, (int)n,
-                       static_cast<double*>(cbuf));
-    hipLaunchKernelGGL(symeig_vectors_kernel<128>, dim3((unsigned)k), dim3(64), vlds, ctx->stream, vp);
-  } else if (n <= 256) {
-    const size_t vlds = sizeof(double) * (8 * 256 + 8) + 256;
-    hipLaunchKernelGGL(symeig_wy_kernel<256>, dim3((unsigned)nblk), dim3(64), 0, ctx->stream, vp.V, (int)n,
-                       static_cast<double*>(cbuf));
-    hipLaunchKernelGGL(symeig_vectors_kernel<256>, dim3((unsigned)k), dim3(64), vlds, ctx->stream, vp);
-  } else {
-    const size_t vlds = sizeof(double) * (8 * 512 + 8) + 512;
-    hipLaunchKernelGGL(symeig_wy_kernel<512>, dim3((unsigned)nblk), dim3(64), 0, ctx->stream, vp.V, (int)n,
-                       static_cast<double*>(cbuf));
-    hipLaunchKernelGGL(symeig_vectors_kernel<512>, dim3((unsigned)k), dim3(64), vlds, ctx->stream, vp);
-  }
-  RT_HIP_CHECK(ctx, hipGetLastError());
-  return RT_OK;
+    hipLaunchKernelGGL(symeig_vectors_kernel<NM>, dim3((unsigned)k), dim3(64), vlds, ctx->stream, vp);
+    RT_HIP_CHECK(ctx, hipGetLastError());
+    return RT_OK;
+  });
 }
