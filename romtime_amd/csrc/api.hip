@@ -4,8 +4,6 @@
 #include <chrono>
 #include <new>
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 int grow(rt_ctx* ctx, void** buf, size_t* have, size_t bytes, void** out) {
@@ -160,6 +158,30 @@ int rt_func_lds(rt_ctx* ctx, const void* fn, int bytes) {
     if (f == fn) return RT_OK;
   RT_HIP_CHECK(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
   ctx->lds_done.push_back(fn);
+  return RT_OK;
+}
+
+int rt_profile_begin(rt_ctx* ctx, bool also_gram) {
+  if (!ctx->profile) return RT_OK;
+  if (!ctx->ev0) {
+    RT_HIP_CHECK(ctx, hipEventCreate(&ctx->ev0));
+    RT_HIP_CHECK(ctx, hipEventCreate(&ctx->ev1));
+  }
+  if (also_gram && !ctx->gev0) {
+    RT_HIP_CHECK(ctx, hipEventCreate(&ctx->gev0));
+    RT_HIP_CHECK(ctx, hipEventCreate(&ctx->gev1));
+  }
+  RT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  if (also_gram) RT_HIP_CHECK(ctx, hipEventRecord(ctx->gev0, ctx->stream));
+  return RT_OK;
+}
+
+int rt_profile_end(rt_ctx* ctx, bool also_gram) {
+  if (!ctx->profile) return RT_OK;
+  RT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  if (also_gram) RT_HIP_CHECK(ctx, hipEventRecord(ctx->gev1, ctx->stream));
+  ctx->ev_valid = true;
+  if (also_gram) ctx->gev_valid = true;
   return RT_OK;
 }
 

@@ -7,6 +7,10 @@
 
 #include "../../include/romtime_hip.h"
 
+// two and four doubles as one register operand: 16- and 32-byte memory accesses, the FP64 MFMA accumulator
+typedef double d2 __attribute__((ext_vector_type(2)));
+typedef double d4 __attribute__((ext_vector_type(4)));
+
 constexpr int RT_N_COUNTERS = 11;
 
 struct rt_ctx {
@@ -95,6 +99,25 @@ int rt_func_lds(rt_ctx* ctx, const void* fn, int bytes);
 int rt_scratch(rt_ctx* ctx, size_t bytes, void** out);
 int rt_scratch2(rt_ctx* ctx, size_t bytes, void** out);
 
+// Carves one arena into 256-byte aligned pieces: add() every piece while planning (it returns the piece's offset),
+// take total() bytes, then at<T>(base, offset) is the piece.
+struct rt_carver {
+  size_t off = 0;
+  size_t add(size_t bytes) {
+    const size_t o = off;
+    off += (bytes + 255) / 256 * 256;
+    return o;
+  }
+  size_t total() const { return off; }
+  template <class T>
+  static T* at(void* base, size_t offset) { return reinterpret_cast<T*>(static_cast<char*>(base) + offset); }
+};
+
+// Profile mode (ctx->profile): bracket the main kernel of an operation with the ctx's event pair (rt_last_kernel_ms);
+// `also_gram`: the Gram kernel's own pair as well.  No-ops outside profile mode.
+int rt_profile_begin(rt_ctx* ctx, bool also_gram = false);
+int rt_profile_end(rt_ctx* ctx, bool also_gram = false);
+
 // Generic strided GEMM on the f64 matrix cores:  C(i,j) = sum_k A(k,i) * B(k,j).
 //   A(k,i) at A[k*a_ks + i*a_ms]  (exactly one of a_ks / a_ms is 1, or M == 1)
 //   B(k,j) at B[k*b_ks + j*b_ns]
@@ -121,10 +144,10 @@ int rt_skinny_tn(rt_ctx* ctx, const double* A, int64_t lda, const double* B, int
                  double* Cm, int64_t ldc);
 
 // Newton-Schulz inverse tracking solve for the online sweep (solve.hip); RT_ERR_UNSUPPORTED for r > 80.
-struct rt_newton_rhs;  // sweep_step.h: how a step's right-hand side is formed ...
+struct rt_step_rhs;  // sweep_step.h: how a step's right-hand side is formed ...
 struct rt_advance;     // ... and how the step is closed, in the solver kernel's tail
 int rt_newton_solve_batched(rt_ctx* ctx, const double* K, double* Xinv, double* rhs, int64_t r, int64_t B,
-                            int have_prev, int* info, const rt_newton_rhs* recipe = nullptr,
+                            int have_prev, int* info, const rt_step_rhs* recipe = nullptr,
                             const rt_advance* advance = nullptr);
 
 // Restarted GMRES with SciPy's control flow (gmres.hip).  `work`: rt_gmres_work_bytes(r, B, o) bytes of device memory for
@@ -133,7 +156,7 @@ int rt_newton_solve_batched(rt_ctx* ctx, const double* K, double* Xinv, double* 
 int rt_gmres_check_opts(rt_ctx* ctx, const rt_gmres_opts* o);
 size_t rt_gmres_work_bytes(int64_t r, int64_t B, const rt_gmres_opts* o);
 int rt_gmres_launch(rt_ctx* ctx, const double* K, const double* b, double* x, int64_t r, int64_t B, const rt_gmres_opts* o,
-                    int64_t* info, int* iters, double* work, const rt_newton_rhs* recipe, const rt_advance* advance,
+                    int64_t* info, int* iters, double* work, const rt_step_rhs* recipe, const rt_advance* advance,
                     bool count);
 
 // Fused SpMM + V^T(.) projection (project_fused.hip); RT_ERR_UNSUPPORTED for r > 128.  `stage_table` is the

@@ -16,8 +16,6 @@
 #include "common.h"
 #include "wave_ops.h"
 
-typedef double d2 __attribute__((ext_vector_type(2)));
-
 namespace {
 
 struct Top2 {
@@ -445,25 +443,19 @@ extern "C" int rt_deim_greedy(rt_ctx* ctx, const double* Phi, int64_t N, int64_t
   const int nparts = (int)((N + RES_ROWS - 1) / RES_ROWS);   // workgroups of the block sweeps
   const int ncol = (int)((N + COL_ROWS - 1) / COL_ROWS);     // workgroups (= argmax partials) of a column's kernel
   // scratch: R | Tb | Linv | delta | YT | pv1 | pv2 | pi1  (the three partial arrays twice: one set per column parity)
-  size_t off = 0;
-  auto take = [&off](size_t bytes) {
-    size_t o = off;
-    off += (bytes + 255) / 256 * 256;
-    return o;
-  };
-  const size_t oR = take(sizeof(double) * ldr * m), oT = take(sizeof(double) * ldr * BLK),
-               oL = take(sizeof(double) * m * m), oD = take(sizeof(double) * m), oYT = take(sizeof(double) * BLK * m),
-               oV1 = take(sizeof(double) * 2 * ncol), oV2 = take(sizeof(double) * 2 * ncol),
-               oI1 = take(sizeof(long) * 2 * ncol);
+  rt_carver a;
+  const size_t oR = a.add(sizeof(double) * ldr * m), oT = a.add(sizeof(double) * ldr * BLK),
+               oL = a.add(sizeof(double) * m * m), oD = a.add(sizeof(double) * m), oYT = a.add(sizeof(double) * BLK * m),
+               oV1 = a.add(sizeof(double) * 2 * ncol), oV2 = a.add(sizeof(double) * 2 * ncol),
+               oI1 = a.add(sizeof(long) * 2 * ncol);
   void* base = nullptr;
-  int rc = rt_scratch2(ctx, off, &base);
+  int rc = rt_scratch2(ctx, a.total(), &base);
   if (rc != RT_OK) return rc;
-  char* b8 = static_cast<char*>(base);
-  double* R = reinterpret_cast<double*>(b8 + oR);
-  double* Tb = reinterpret_cast<double*>(b8 + oT);
-  double* Linv = reinterpret_cast<double*>(b8 + oL);
-  double* delta = reinterpret_cast<double*>(b8 + oD);
-  double* YT = reinterpret_cast<double*>(b8 + oYT);
+  double* R = a.at<double>(base, oR);
+  double* Tb = a.at<double>(base, oT);
+  double* Linv = a.at<double>(base, oL);
+  double* delta = a.at<double>(base, oD);
+  double* YT = a.at<double>(base, oYT);
   hipStream_t st = ctx->stream;
 
   RT_HIP_CHECK(ctx, hipMemsetAsync(Linv, 0, sizeof(double) * m * m, st));
@@ -471,8 +463,8 @@ extern "C" int rt_deim_greedy(rt_ctx* ctx, const double* Phi, int64_t N, int64_t
   // coefficients) and one sweep (phase A) that applies all earlier residual columns, then one launch per column:
   // the column's kernel finishes the step before it in every workgroup and reduces the column against at most
   // BLK-1 in-block columns.  HBM traffic drops from ~4 N m^2 to ~4 N m^2 / BLK + 4 N m (BLK + 7) bytes.
-  const StepState state{(int)m, ncol, reinterpret_cast<double*>(b8 + oV1), reinterpret_cast<long*>(b8 + oI1),
-                        reinterpret_cast<double*>(b8 + oV2), reinterpret_cast<long*>(idx), delta, margin, Linv};
+  const StepState state{(int)m, ncol, a.at<double>(base, oV1), a.at<long>(base, oI1),
+                        a.at<double>(base, oV2), reinterpret_cast<long*>(idx), delta, margin, Linv};
   RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&deim_phase_a_kernel), 1024 * BLK * 8));
   for (int k0 = 0; k0 < (int)m; k0 += BLK) {
     const int nb = ((int)m - k0 < BLK) ? (int)m - k0 : BLK;

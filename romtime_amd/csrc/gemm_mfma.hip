@@ -277,13 +277,7 @@ int rt_gemm_strided(rt_ctx* ctx, const double* A, int64_t a_ks, int64_t a_ms, co
   ctx->last_grid = grid; ctx->last_splits = splits; ctx->last_tile = BM * 1000 + BN;
 
   int rc = RT_OK;
-  if (ctx->profile) {
-    if (!ctx->ev0) {
-      RT_HIP_CHECK(ctx, hipEventCreate(&ctx->ev0));
-      RT_HIP_CHECK(ctx, hipEventCreate(&ctx->ev1));
-    }
-    RT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  }
+  RT_TRY(rt_profile_begin(ctx));
   if (skinny) {
     switch (snt) {
       case 1: rc = launch_skinny<1>(ctx, p, grid, kca, kcb); break;
@@ -299,10 +293,7 @@ int rt_gemm_strided(rt_ctx* ctx, const double* A, int64_t a_ks, int64_t a_ms, co
     default: rc = launch_nt<4>(ctx, p, grid, nt, kca, kcb); break;
   }
   if (rc != RT_OK) return rc;
-  if (ctx->profile) {
-    RT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    ctx->ev_valid = true;
-  }
+  RT_TRY(rt_profile_end(ctx));
   if (use_slab) {
     const long total = M * Nn;
     hipLaunchKernelGGL(gemm_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream,

@@ -2,9 +2,6 @@
 #pragma once
 #include "common.h"
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-typedef double d2 __attribute__((ext_vector_type(2)));
-
 namespace rtk {
 
 constexpr int KB = 16;            // contraction depth per LDS stage (4 MFMA k-steps)

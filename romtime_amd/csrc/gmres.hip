@@ -125,7 +125,7 @@ template <int NV, bool LDSB>
 __global__ __launch_bounds__(GM_THREADS) void gmres_kernel(const double* __restrict__ K, const double* __restrict__ bsrc,
                                                            double* __restrict__ xout, int r, const gm_params p,
                                                            int64_t* __restrict__ info, int* __restrict__ iters,
-                                                           double* __restrict__ work, const rt_newton_rhs rq,
+                                                           double* __restrict__ work, const rt_step_rhs rq,
                                                            long* __restrict__ counters, const rt_advance adv) {
   extern __shared__ __attribute__((aligned(16))) double gm_sm[];
   constexpr int ST = 64 * NV;   // stride of a lane-distributed vector in the basis / R storage
@@ -163,21 +163,15 @@ __global__ __launch_bounds__(GM_THREADS) void gmres_kernel(const double* __restr
 #pragma unroll
     for (int q = 0; q < NV; ++q) {
       const int i = lane + 64 * q;
-      su[q] = (i < r) ? rq.c0 * rq.un[(size_t)sys * r + i] + rq.c1 * rq.unm1[(size_t)sys * r + i] : 0.0;
+      su[q] = (i < r) ? step_rhs_state(rq, sys, r, i) : 0.0;
     }
     gm_to_lds<NV>(sv, su, r, lane);
-    const double* Mb = rq.MN + (size_t)sys * (rq.mn_stride < 0 ? (long)r * r : rq.mn_stride);
-    const double* Ff = rq.mf ? (rq.ctr ? rq.Ff + *rq.ctr * rq.ff_stride : rq.Ff) + (size_t)sys * rq.mf : nullptr;
+    const double* Mb = step_rhs_mn(rq, sys, r);
+    const double* Ff = step_rhs_forcing_rows(rq, sys);
 #pragma unroll
     for (int q = 0; q < NV; ++q) {
       const int i = lane + 64 * q;
-      double acc = 0.0, f = 0.0;
-      if (i < r) {
-        const double* Mrow = Mb + (size_t)i * r;
-        for (int j = 0; j < r; ++j) acc = fma(Mrow[j], sv[j], acc);
-        for (int e = 0; e < rq.mf; ++e) f = fma(Ff[e], rq.Zf[(size_t)e * r + i], f);
-      }
-      bv[q] = (i < r) ? fma(rq.dt, f, acc) : 0.0;
+      bv[q] = (i < r) ? step_rhs_row(rq, Mb, Ff, r, i, sv) : 0.0;
     }
   } else {
 #pragma unroll
@@ -357,7 +351,7 @@ size_t rt_gmres_work_bytes(int64_t r, int64_t B, const rt_gmres_opts* o) {
 }
 
 int rt_gmres_launch(rt_ctx* ctx, const double* K, const double* b, double* x, int64_t r, int64_t B, const rt_gmres_opts* o,
-                    int64_t* info, int* iters, double* work, const rt_newton_rhs* recipe, const rt_advance* advance,
+                    int64_t* info, int* iters, double* work, const rt_step_rhs* recipe, const rt_advance* advance,
                     bool count) {
   RT_TRY(rt_gmres_check_opts(ctx, o));
   if (r > 128) {
@@ -374,8 +368,7 @@ int rt_gmres_launch(rt_ctx* ctx, const double* K, const double* b, double* x, in
     RT_TRY(rt_scratch(ctx, (size_t)B * gm_vec_bytes(r, m), &w));
     work = static_cast<double*>(w);
   }
-  rt_newton_rhs rq{};
-  if (recipe) rq = *recipe;
+  const rt_step_rhs rq = recipe ? *recipe : rt_step_rhs{};
   const rt_advance adv = advance ? *advance : rt_advance{};
   long* counters = count ? ctx->dev_counters : nullptr;
   double* wk = in_lds ? nullptr : work;

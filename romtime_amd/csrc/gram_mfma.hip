@@ -522,18 +522,7 @@ int rt_gram128(rt_ctx* ctx, const double* X, int64_t ks, int64_t ms, int64_t K, 
   rp.slab_off = slab_off; rp.slab_diag = slab_diag; rp.G = G; rp.n = n; rp.last0 = p.last0;
   rp.nslots_off = nslots_off; rp.nslots_diag = nslots_diag; rp.tiles1 = tiles1; rp.pace = ctx->gram_pace;
 
-  if (ctx->profile) {
-    if (!ctx->ev0) {
-      RT_HIP_CHECK(ctx, hipEventCreate(&ctx->ev0));
-      RT_HIP_CHECK(ctx, hipEventCreate(&ctx->ev1));
-    }
-    if (!ctx->gev0) {
-      RT_HIP_CHECK(ctx, hipEventCreate(&ctx->gev0));
-      RT_HIP_CHECK(ctx, hipEventCreate(&ctx->gev1));
-    }
-    RT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    RT_HIP_CHECK(ctx, hipEventRecord(ctx->gev0, ctx->stream));
-  }
+  RT_TRY(rt_profile_begin(ctx, true));
   if (one_launch) {
     p.slab = slab_off; p.nslots = nslots_off;
     rc = kc ? launch_gram_merged<true>(ctx, p, g, 8 * c.slots) : launch_gram_merged<false>(ctx, p, g, 8 * c.slots);
@@ -573,12 +562,7 @@ int rt_gram128(rt_ctx* ctx, const double* X, int64_t ks, int64_t ms, int64_t K, 
       if (rc != RT_OK) return rc;
     }
   }
-  if (ctx->profile) {
-    RT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    RT_HIP_CHECK(ctx, hipEventRecord(ctx->gev1, ctx->stream));
-    ctx->ev_valid = true;
-    ctx->gev_valid = true;
-  }
+  RT_TRY(rt_profile_end(ctx, true));
   ctx->last_grid = one_launch ? 8 * c.slots : 8 * (nslots_off + nslots_diag);
   ctx->last_splits = 8 * (one_launch ? c.a : c.s_off);
   ctx->last_tile = 128 * 1000 + 128;

@@ -45,8 +45,6 @@
 #define PF_ABLATE(bit) false
 #endif
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-typedef double d2 __attribute__((ext_vector_type(2)));
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
 
 namespace {
@@ -536,19 +534,6 @@ static int fused_blocks_per_cu(rt_ctx* ctx, int* out) {
   return RT_OK;
 }
 
-static int fused_blocks_per_cu(rt_ctx* ctx, int tr, int* out) {
-  switch (tr) {
-    case 1: return fused_blocks_per_cu<1>(ctx, out);
-    case 2: return fused_blocks_per_cu<2>(ctx, out);
-    case 3: return fused_blocks_per_cu<3>(ctx, out);
-    case 4: return fused_blocks_per_cu<4>(ctx, out);
-    case 5: return fused_blocks_per_cu<5>(ctx, out);
-    case 6: return fused_blocks_per_cu<6>(ctx, out);
-    case 7: return fused_blocks_per_cu<7>(ctx, out);
-    default: return fused_blocks_per_cu<8>(ctx, out);
-  }
-}
-
 template <int TR>
 static int launch_fused(rt_ctx* ctx, const ProjParams& p, unsigned grid, int banded) {
   if (banded != 0)
@@ -584,7 +569,7 @@ int rt_project_fused(rt_ctx* ctx, const int64_t* indptr, const int64_t* indices,
   // resident workgroups ran 2.1 rounds' worth of work in 3 rounds (C4's projection at 0.36 of the MFMA peak next
   // to C5's 0.51 with 32 x 32 = exactly two rounds); 120 x 8 = 960 fills 2 rounds to 94 %.
   int per_cu = 1;
-  int rc0 = fused_blocks_per_cu(ctx, tr, &per_cu);
+  int rc0 = tile_rows_dispatch(tr, [&](auto t) { return fused_blocks_per_cu<decltype(t)::value>(ctx, &per_cu); });
   if (rc0 != RT_OK) return rc0;
   const long resident = (long)per_cu * ctx->num_cus;
   const long stages = (N + PK - 1) / PK;
@@ -624,30 +609,12 @@ int rt_project_fused(rt_ctx* ctx, const int64_t* indptr, const int64_t* indices,
     p.any_unwindowed = static_cast<const int*>(table);
     p.rec = reinterpret_cast<const StageRec*>(static_cast<const char*>(table) + TABLE_HEADER);
   }
-  if (ctx->profile) {
-    if (!ctx->ev0) {
-      RT_HIP_CHECK(ctx, hipEventCreate(&ctx->ev0));
-      RT_HIP_CHECK(ctx, hipEventCreate(&ctx->ev1));
-    }
-    RT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  }
+  RT_TRY(rt_profile_begin(ctx));
   p.xcd_map = 1;
   const unsigned grid = (unsigned)(((B * S + 7) / 8) * 8);   // whole eighths of the work list, one per XCD
-  switch (tr) {
-    case 1: rc = launch_fused<1>(ctx, p, grid, banded); break;
-    case 2: rc = launch_fused<2>(ctx, p, grid, banded); break;
-    case 3: rc = launch_fused<3>(ctx, p, grid, banded); break;
-    case 4: rc = launch_fused<4>(ctx, p, grid, banded); break;
-    case 5: rc = launch_fused<5>(ctx, p, grid, banded); break;
-    case 6: rc = launch_fused<6>(ctx, p, grid, banded); break;
-    case 7: rc = launch_fused<7>(ctx, p, grid, banded); break;
-    default: rc = launch_fused<8>(ctx, p, grid, banded); break;
-  }
+  rc = tile_rows_dispatch(tr, [&](auto t) { return launch_fused<decltype(t)::value>(ctx, p, grid, banded); });
   if (rc != RT_OK) return rc;
-  if (ctx->profile) {
-    RT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    ctx->ev_valid = true;
-  }
+  RT_TRY(rt_profile_end(ctx));
   const long rr = r * r, total = B * rr;
   hipLaunchKernelGGL(project_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream,
                      p.slab, (int)S, rr, total, AN);

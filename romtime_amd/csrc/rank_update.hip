@@ -7,8 +7,6 @@
 // replaces the clone of the caller's snapshots and, with d, their column normalisation.
 #include "common.h"
 
-typedef double d2 __attribute__((ext_vector_type(2)));
-
 namespace {
 
 constexpr int RU_THREADS = 256;

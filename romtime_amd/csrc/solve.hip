@@ -18,9 +18,6 @@
 #include "sweep_step.h"
 #include "tile_layout.h"
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-typedef double d2 __attribute__((ext_vector_type(2)));
-
 namespace {
 
 constexpr int SOLVE_THREADS = 256;
@@ -213,52 +210,48 @@ constexpr int NS_REFRESH_AFTER = 5;      // more steps than this: the answer sta
 constexpr double NS_REFINE_TOL = 2e-15;  // ||b - K x|| <= tol ||b||: the floor of a refinement in working precision
 constexpr double NS_REFINE_RATE = 0.3;   // a step must shrink the residual at least this much, or X is not worth keeping
 
-__device__ __forceinline__ double ns_block_sum(double x, double* s_red, int tid) {
-  x = rtw::wave_sum(x);
+enum NsOp { NS_SUM, NS_MAX };
+// Sum or maximum of x over the workgroup: the waves' partials go through s_red and every thread combines them in wave
+// order.  The maximum starts from the first wave's partial; the sum starts from +0.0 and ADDS the first partial to it,
+// an addition kept on purpose: it makes eight partials of -0.0 come out as +0.0, as they always have.  (A build with
+// -fno-signed-zeros or -ffast-math would fold it away; the build's flags must stay without them.)
+template <NsOp OP>
+__device__ __forceinline__ double ns_block_reduce(double x, double* s_red, int tid) {
+  x = OP == NS_MAX ? rtw::wave_max(x) : rtw::wave_sum(x);
   __syncthreads();
   if ((tid & 63) == 0) s_red[tid >> 6] = x;
   __syncthreads();
-  double t = 0.0;
+  double t = OP == NS_MAX ? s_red[0] : 0.0 + s_red[0];
 #pragma unroll
-  for (int w = 0; w < NS_THREADS / 64; ++w) t += s_red[w];
+  for (int w = 1; w < NS_THREADS / 64; ++w) t = OP == NS_MAX ? fmax(t, s_red[w]) : t + s_red[w];
   return t;
 }
 
-__device__ __forceinline__ double ns_block_max(double x, double* s_red, int tid) {
-  x = rtw::wave_max(x);
-  __syncthreads();
-  if ((tid & 63) == 0) s_red[tid >> 6] = x;
-  __syncthreads();
-  double t = s_red[0];
-#pragma unroll
-  for (int w = 1; w < NS_THREADS / 64; ++w) t = fmax(t, s_red[w]);
-  return t;
-}
+constexpr int NS_NBI = 2, NS_NBJ = 3;   // a wave's block of output tiles is at most 2 x 3 for r <= 80 (tile_layout.h)
+typedef d4 NsAcc[NS_NBI][NS_NBJ];
 
-__global__ __launch_bounds__(NS_THREADS) void newton_solve_kernel(const double* __restrict__ K,
-                                                                  double* __restrict__ Xinv,
-                                                                  double* __restrict__ rhs, int r, int S,
-                                                                  int have_prev, int* __restrict__ info,
-                                                                  const rt_newton_rhs rq, long* counters,
-                                                                  const rt_advance adv) {
-  extern __shared__ __attribute__((aligned(16))) double sm[];
-  const int tr = (r + 15) / 16, rp = tr * 16;
-  double* sK = sm;                    // [rp][S], padded with the identity
-  double* sX = sK + (size_t)rp * S;   // [rp][S]
-  double* sT = sX + (size_t)rp * S;   // [rp][S]
-  __shared__ double s_red[NS_THREADS / 64];
-  __shared__ double s_vec[4][96];   // r <= 80 here (three padded r x r matrices in the dynamic part)
-  const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, l4 = lane >> 4;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const double* Kb = K + (size_t)blockIdx.x * r * r;
-  double* Xb = Xinv + (size_t)blockIdx.x * r * r;
-  double* rb = rhs + (size_t)blockIdx.x * r;
+// How a system's solve ended (NsGroup::finish closes the step for all four), and what Newton-Schulz reports
+enum NsRoute {
+  NS_KEPT,            // the refinement solved it and X is good for the steps to come
+  NS_REFRESHED,       // Newton-Schulz converged: X goes back refreshed
+  NS_REFRESH_FAILED,  // the refinement solved it, the refresh of X did not converge
+  NS_LU               // neither did: pivoted LU of the workgroup's copy of K
+};
+struct NsOutcome { int status, iters, restarts; };
+
+// One workgroup's view of its system: the three padded matrices in LDS, the four work vectors, the thread's place.
+// The stages of newton_solve_kernel are its members; all threads call each of them.
+struct NsGroup {
+  double *sK, *sX, *sT;   // [rp][S] each; sK padded with the identity
+  double (*s_vec)[96];    // 0: b, 1: x, 2 and 3: scratch
+  double* s_red;
+  int r, rp, S, tid, lane, wid;
 
   // out_i = sum_j A[i][j] v[j] for the r rows of an LDS matrix (A, v, out in LDS; out may not be v): eight lanes
   // share a row (columns j == lane mod 8) and add up with three butterfly steps, 64 rows per pass of the workgroup.
   // No LDS scratch: the three padded matrices leave 3 KB of the CU's 160.  (One thread per row walked r LDS round
   // trips one after the other, four times per solve.)
-  auto matvec = [&](const double* A, const double* v, double* out) {
+  __device__ __forceinline__ void matvec(const double* A, const double* v, double* out) const {
     const int sub = lane & 7;
     for (int i0 = 0; i0 < r; i0 += NS_THREADS / 8) {
       const int i = i0 + (tid >> 3);
@@ -273,123 +266,144 @@ __global__ __launch_bounds__(NS_THREADS) void newton_solve_kernel(const double* 
       if (i < r && sub == 0) out[i] = acc;
     }
     __syncthreads();
-  };
+  }
 
-  // K, the carried inverse and (when the right-hand side is formed here) M_N come in together: one round of global
-  // loads, M_N parked in sT until the first product needs the space
-  const double* Mb = rq.MN ? rq.MN + (size_t)blockIdx.x * (rq.mn_stride < 0 ? (long)r * r : rq.mn_stride) : nullptr;
-  const bool wide_ok = (r == rp) && ((reinterpret_cast<size_t>(Kb) | reinterpret_cast<size_t>(Xb) | reinterpret_cast<size_t>(Mb)) & 15) == 0;
-  if (wide_ok) {
-    // r a multiple of 16: a row is r / 2 <= 40 pairs, one 16-byte load per lane and row; the <= 10 rows of a wave
-    // for all three matrices are in flight together
-    constexpr int QMAX = 10;
-    d2 kv[QMAX], xv[QMAX], mv[QMAX];
-    const int j = 2 * lane;
+  // K, the carried inverse and (when the right-hand side is formed here: Mb != nullptr) M_N come in together: one
+  // round of global loads, M_N parked in sT until the first product needs the space.  `wide`: r is a multiple of 16
+  // and the three operands are 16-byte aligned.  Ends without a barrier.
+  __device__ __forceinline__ void load(const double* Kb, const double* Xb, const double* Mb, int have_prev,
+                                       bool wide) const {
+    if (wide) {
+      // a row is r / 2 <= 40 pairs, one 16-byte load per lane and row; the <= 10 rows of a wave for all three
+      // matrices are in flight together
+      constexpr int QMAX = 10;
+      d2 kv[QMAX], xv[QMAX], mv[QMAX];
+      const int j = 2 * lane;
 #pragma unroll
-    for (int q = 0; q < QMAX; ++q) {
-      const int i = wid + 8 * q;
-      const bool in = i < r && j < r;
-      kv[q] = in ? *reinterpret_cast<const d2*>(Kb + i * r + j) : d2{0.0, 0.0};
-      xv[q] = (in && have_prev) ? *reinterpret_cast<const d2*>(Xb + i * r + j) : d2{i == j ? 1.0 : 0.0, i == j + 1 ? 1.0 : 0.0};
-      mv[q] = (in && Mb) ? *reinterpret_cast<const d2*>(Mb + i * r + j) : d2{0.0, 0.0};
-    }
+      for (int q = 0; q < QMAX; ++q) {
+        const int i = wid + 8 * q;
+        const bool in = i < r && j < r;
+        kv[q] = in ? *reinterpret_cast<const d2*>(Kb + i * r + j) : d2{0.0, 0.0};
+        xv[q] = (in && have_prev) ? *reinterpret_cast<const d2*>(Xb + i * r + j) : d2{i == j ? 1.0 : 0.0, i == j + 1 ? 1.0 : 0.0};
+        mv[q] = (in && Mb) ? *reinterpret_cast<const d2*>(Mb + i * r + j) : d2{0.0, 0.0};
+      }
 #pragma unroll
-    for (int q = 0; q < QMAX; ++q) {
-      const int i = wid + 8 * q;
-      if (i < r && j < r) {
-        *reinterpret_cast<d2*>(sK + i * S + j) = kv[q];
-        *reinterpret_cast<d2*>(sX + i * S + j) = xv[q];
-        if (Mb) *reinterpret_cast<d2*>(sT + i * S + j) = mv[q];
+      for (int q = 0; q < QMAX; ++q) {
+        const int i = wid + 8 * q;
+        if (i < r && j < r) {
+          *reinterpret_cast<d2*>(sK + i * S + j) = kv[q];
+          *reinterpret_cast<d2*>(sX + i * S + j) = xv[q];
+          if (Mb) *reinterpret_cast<d2*>(sT + i * S + j) = mv[q];
+        }
+      }
+    } else {
+      // rp <= 80: a wave has at most 10 rows (i = wid + 8 q) of at most 2 x 64 columns.  Fixed trip counts, loads of
+      // half the rows issued before any LDS store: a loop over runtime bounds went load - wait - store twenty times
+      constexpr int QH = 5;
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        double kv[QH][2], xv[QH][2], mv[QH][2];
+#pragma unroll
+        for (int q = 0; q < QH; ++q)
+#pragma unroll
+          for (int c = 0; c < 2; ++c) {
+            const int i = wid + 8 * (QH * half + q), j = lane + 64 * c;
+            const bool in = i < r && j < r;
+            const double eye = (i == j) ? 1.0 : 0.0;
+            kv[q][c] = in ? Kb[i * r + j] : eye;
+            xv[q][c] = (in && have_prev) ? Xb[i * r + j] : eye;
+            mv[q][c] = (in && Mb) ? Mb[i * r + j] : 0.0;
+          }
+#pragma unroll
+        for (int q = 0; q < QH; ++q)
+#pragma unroll
+          for (int c = 0; c < 2; ++c) {
+            const int i = wid + 8 * (QH * half + q), j = lane + 64 * c;
+            if (i < rp && j < rp) {
+              sK[i * S + j] = kv[q][c];
+              sX[i * S + j] = xv[q][c];
+              if (Mb) sT[i * S + j] = mv[q][c];
+            }
+          }
       }
     }
-  } else {
-    // rp <= 80: a wave has at most 10 rows (i = wid + 8 q) of at most 2 x 64 columns.  Fixed trip counts, loads of
-    // half the rows issued before any LDS store: a loop over runtime bounds went load - wait - store twenty times
-    constexpr int QH = 5;
+  }
+
+  // The refreshed inverse goes back the way it came: one 16-byte store per lane and row, or entry by entry
+  __device__ __forceinline__ void store_X(double* Xb, bool wide) const {
+    if (wide) {
+      const int j = 2 * lane;
+      d2 xv[10];
 #pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      double kv[QH][2], xv[QH][2], mv[QH][2];
+      for (int q = 0; q < 10; ++q) {
+        const int i = wid + 8 * q;
+        if (i < r && j < r) xv[q] = *reinterpret_cast<const d2*>(sX + i * S + j);
+      }
 #pragma unroll
-      for (int q = 0; q < QH; ++q)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          const int i = wid + 8 * (QH * half + q), j = lane + 64 * c;
-          const bool in = i < r && j < r;
-          const double eye = (i == j) ? 1.0 : 0.0;
-          kv[q][c] = in ? Kb[i * r + j] : eye;
-          xv[q][c] = (in && have_prev) ? Xb[i * r + j] : eye;
-          mv[q][c] = (in && Mb) ? Mb[i * r + j] : 0.0;
-        }
-#pragma unroll
-      for (int q = 0; q < QH; ++q)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          const int i = wid + 8 * (QH * half + q), j = lane + 64 * c;
-          if (i < rp && j < rp) {
-            sK[i * S + j] = kv[q][c];
-            sX[i * S + j] = xv[q][c];
-            if (Mb) sT[i * S + j] = mv[q][c];
-          }
-        }
+      for (int q = 0; q < 10; ++q) {
+        const int i = wid + 8 * q;
+        if (i < r && j < r) *reinterpret_cast<d2*>(Xb + i * r + j) = xv[q];
+      }
+    } else {
+      for (int i = wid; i < r; i += NS_THREADS / 64)
+        for (int j = lane; j < r; j += 64) Xb[i * r + j] = sX[i * S + j];
     }
   }
-  if (rq.MN) {
-    // right-hand side: b = M_N (c0 u^n + c1 u^{n-1}) + dt Zf^T F_rhs (also left in rhs for the fallback); row i is
-    // thread i's: r FMAs out of LDS and mf independent loads - a wave per row with a cross-lane sum took a chain
-    // of r / 8 global round trips per wave
-    if (tid < r) s_vec[1][tid] = rq.c0 * rq.un[(size_t)blockIdx.x * r + tid] + rq.c1 * rq.unm1[(size_t)blockIdx.x * r + tid];
+
+  // b into s_vec[0], visible on return.  With a recipe: b = M_N (c0 u^n + c1 u^{n-1}) + dt Zf^T F_rhs, M_N out of sT
+  // (also left in rb for the fallback); row i is thread i's: r FMAs out of LDS and mf independent loads - a wave per
+  // row with a cross-lane sum took a chain of r / 8 global round trips per wave.  Without: rb is given.
+  __device__ __forceinline__ void right_hand_side(const rt_step_rhs& rq, int b, double* rb) const {
+    if (rq.MN) {
+      if (tid < r) s_vec[1][tid] = step_rhs_state(rq, b, r, tid);
+      __syncthreads();
+      const double f = (tid < r) ? step_rhs_forcing(rq, step_rhs_forcing_rows(rq, b), r, tid) : 0.0;
+      matvec(sT, s_vec[1], s_vec[2]);
+      if (tid < r) {
+        const double v = fma(rq.dt, f, s_vec[2][tid]);
+        s_vec[0][tid] = v;
+        rb[tid] = v;
+      }
+    } else if (tid < r) {
+      s_vec[0][tid] = rb[tid];
+    }
     __syncthreads();
-    double f = 0.0;
-    if (tid < r) {
-      const double* Ff = (rq.ctr ? rq.Ff + *rq.ctr * rq.ff_stride : rq.Ff) + (size_t)blockIdx.x * rq.mf;
-      for (int e = 0; e < rq.mf; ++e) f = fma(Ff[e], rq.Zf[(size_t)e * r + tid], f);
-    }
-    matvec(sT, s_vec[1], s_vec[2]);
-    if (tid < r) {
-      const double v = fma(rq.dt, f, s_vec[2][tid]);
-      s_vec[0][tid] = v;
-      rb[tid] = v;
-    }
-  } else if (tid < r) {
-    s_vec[0][tid] = rb[tid];
   }
-  __syncthreads();
 
   // C(ti, tj) = sum_k A[16 ti + i][k] B[k][16 tj + j] on the matrix cores, operands out of LDS.  A wave owns one
-  // rectangular block of tiles (tile_layout.h; at most 2 x 3 for r <= 80), so a k-step costs ni + nj LDS reads for
-  // ni nj MFMAs (scattered tiles t = wid + 8 q read two operands per MFMA and took 9 us per 80^3 product).
-  constexpr int NBI = 2, NBJ = 3;
-  const Blk bk = tile_block(tr, wid);
-  auto tiles_product = [&](const double* A, const double* Bm, d4 (&acc)[NBI][NBJ]) {
-    const double* ap[NBI];
-    const double* bp[NBJ];
+  // rectangular block of tiles, so a k-step costs ni + nj LDS reads for ni nj MFMAs (scattered tiles t = wid + 8 q
+  // read two operands per MFMA and took 9 us per 80^3 product).
+  __device__ __forceinline__ void tiles_product(const Blk& bk, const double* A, const double* Bm, NsAcc& acc) const {
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const double* ap[NS_NBI];
+    const double* bp[NS_NBJ];
 #pragma unroll
-    for (int i = 0; i < NBI; ++i) ap[i] = A + (16 * (bk.i0 + (i < bk.ni ? i : 0)) + l15) * S + l4;
+    for (int i = 0; i < NS_NBI; ++i) ap[i] = A + (16 * (bk.i0 + (i < bk.ni ? i : 0)) + l15) * S + l4;
 #pragma unroll
-    for (int j = 0; j < NBJ; ++j) bp[j] = Bm + l4 * S + 16 * (bk.j0 + (j < bk.nj ? j : 0)) + l15;
+    for (int j = 0; j < NS_NBJ; ++j) bp[j] = Bm + l4 * S + 16 * (bk.j0 + (j < bk.nj ? j : 0)) + l15;
 #pragma unroll
-    for (int i = 0; i < NBI; ++i)
+    for (int i = 0; i < NS_NBI; ++i)
 #pragma unroll
-      for (int j = 0; j < NBJ; ++j) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
+      for (int j = 0; j < NS_NBJ; ++j) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
     for (int k16 = 0; k16 < rp / 16; ++k16)   // rp is a multiple of 16: four k-steps per trip, unrolled
 #pragma unroll
     for (int ku = 0; ku < 4; ++ku) {
       const int k4 = 4 * k16 + ku;
-      double a[NBI], bq[NBJ];
+      double a[NS_NBI], bq[NS_NBJ];
 #pragma unroll
-      for (int i = 0; i < NBI; ++i) a[i] = ap[i][4 * k4];
+      for (int i = 0; i < NS_NBI; ++i) a[i] = ap[i][4 * k4];
 #pragma unroll
-      for (int j = 0; j < NBJ; ++j) bq[j] = bp[j][4 * k4 * S];
+      for (int j = 0; j < NS_NBJ; ++j) bq[j] = bp[j][4 * k4 * S];
 #pragma unroll
-      for (int i = 0; i < NBI; ++i)
+      for (int i = 0; i < NS_NBI; ++i)
 #pragma unroll
-        for (int j = 0; j < NBJ; ++j)
+        for (int j = 0; j < NS_NBJ; ++j)
           if (i < bk.ni && j < bk.nj)  // wave-uniform
             acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], bq[j], acc[i][j], 0, 0, 0);
     }
-  };
+  }
 
-  auto restart = [&]() {  // X = K^T / (||K||_1 ||K||_inf)
+  __device__ __forceinline__ void restart() const {  // X = K^T / (||K||_1 ||K||_inf)
     double rs = 0.0, cs = 0.0;
     if (tid < r) {
       for (int j = 0; j < r; ++j) {
@@ -397,28 +411,25 @@ __global__ __launch_bounds__(NS_THREADS) void newton_solve_kernel(const double* 
         cs += fabs(sK[j * S + tid]);
       }
     }
-    const double ninf = ns_block_max(rs, s_red, tid);
-    const double n1 = ns_block_max(cs, s_red, tid);
+    const double ninf = ns_block_reduce<NS_MAX>(rs, s_red, tid);
+    const double n1 = ns_block_reduce<NS_MAX>(cs, s_red, tid);
     const double sc = 1.0 / (n1 * ninf);
     for (int i = wid; i < rp; i += NS_THREADS / 64)
       for (int j = lane; j < rp; j += 64) sX[i * S + j] = (i < r && j < r) ? sK[j * S + i] * sc : ((i == j) ? 1.0 : 0.0);
     __syncthreads();
-  };
-  if (!have_prev) restart();
+  }
 
-  // Round 3 - refinement before refreshment.  The carried inverse is a PRECONDITIONER: x <- x + X (b - K x) contracts
-  // the error by ||I - X K|| per step, two r x r mat-vecs each, against the two r^3 products of a Newton-Schulz update.
+  // Refinement before refreshment.  The carried inverse is a PRECONDITIONER: x <- x + X (b - K x) contracts the error
+  // by ||I - X K|| per step, two r x r mat-vecs each, against the two r^3 products of a Newton-Schulz update.
   // X was exact to ~1e-8 when it was last refreshed and K has moved by O(dt) per time step since, so a few refinement
   // steps reach the residual floor for many time steps in a row; only when they take more than NS_REFRESH_AFTER steps
   // (or do not contract) is X refreshed - and in the first case the answer is already there, the refresh is for the
-  // steps to come.  31 -> ~15 us per step for 32 systems of 80 (bench.py, hyper-reduced sweep).
-  bool solved = false, refresh = true;
-  if (have_prev) {
+  // steps to come.  31 -> ~15 us per step for 32 systems of 80.  Returns whether x (s_vec[1]) is the answer, in `used` steps.
+  __device__ __forceinline__ bool refine(int& used) const {
     double bpart = (tid < r) ? s_vec[0][tid] * s_vec[0][tid] : 0.0;
-    const double bnorm2 = ns_block_sum(bpart, s_red, tid);
+    const double bnorm2 = ns_block_reduce<NS_SUM>(bpart, s_red, tid);
     matvec(sX, s_vec[0], s_vec[1]);                        // x = X b
     double prev = 1e300;
-    int used = 0;
     for (int it = 0; it <= NS_REFINE_MAX; ++it) {
       matvec(sK, s_vec[1], s_vec[2]);                      // K x
       double rr = 0.0;
@@ -427,12 +438,11 @@ __global__ __launch_bounds__(NS_THREADS) void newton_solve_kernel(const double* 
         s_vec[2][tid] = e;
         rr = e * e;
       }
-      const double rn2 = ns_block_sum(rr, s_red, tid);     // barriers inside: the residual vector is complete
+      const double rn2 = ns_block_reduce<NS_SUM>(rr, s_red, tid);   // barriers inside: the residual vector is complete
       if (!(rn2 == rn2)) break;                             // NaN: leave it to the tracked route and its fallbacks
       if (rn2 <= NS_REFINE_TOL * NS_REFINE_TOL * bnorm2 || (it > 0 && rn2 >= 0.25 * prev && rn2 <= 1e-26 * bnorm2)) {
-        solved = true;                                      // at the floor (or within a hair of it and no longer moving)
-        used = it;
-        break;
+        used = it;                                          // at the floor (or within a hair of it and no longer moving)
+        return true;
       }
       if (it == NS_REFINE_MAX || rn2 > NS_REFINE_RATE * NS_REFINE_RATE * prev) break;   // out of steps / no contraction
       prev = rn2;
@@ -440,107 +450,52 @@ __global__ __launch_bounds__(NS_THREADS) void newton_solve_kernel(const double* 
       if (tid < r) s_vec[1][tid] += s_vec[3][tid];
       __syncthreads();
     }
-    if (solved) {
-      refresh = used > NS_REFRESH_AFTER;
-      if (tid < r) rb[tid] = s_vec[1][tid];
-      if (!refresh) {                                       // X stays as it is: nothing to write back
-        if (tid == 0) atomicAdd(reinterpret_cast<unsigned long long*>(&counters[RT_CNT_SOLVES]), 1ull);
-        if (info && tid == 0) info[blockIdx.x] = 0;
-        if (adv.enabled) {
-          __syncthreads();
-          hsweep_advance_rows(adv, blockIdx.x, r, rhs, 1, s_vec[1], tid, NS_THREADS);
-        }
-        return;
+    return false;
+  }
+
+  // X <- X (2 I - K X) until the residual ||I - K X||_F before the last update was < 1e-6; `restarted`: X is the safe
+  // start already.  status 0, or RT_WARN_SINGULAR: NaN, or no convergence in NS_MAX_ITER updates.  The wave's block
+  // of tiles is looked up HERE: the look-up is a read of constant memory, and in front of the kernel's first loads,
+  // where every route pays for it, it made the sweeps' step 0.3 us slower (with a late exit of the common route).
+  __device__ __forceinline__ NsOutcome newton_schulz(bool restarted) const {
+    const Blk bk = tile_block(rp / 16, wid);
+    NsOutcome o{RT_WARN_SINGULAR, 0, 0};
+    for (int it = 0; it < NS_MAX_ITER; ++it) {
+      ++o.iters;
+      // T = K X and the residual ||I - T||_F
+      double part = 0.0;
+      NsAcc acc;
+      tiles_product(bk, sK, sX, acc);
+      tile_block_entries<NS_NBI, NS_NBJ>(bk, lane, [&](int i, int j, int c, int row, int col) {
+        sT[row * S + col] = acc[i][j][c];
+        const double e = ((row == col) ? 1.0 : 0.0) - acc[i][j][c];
+        part = fma(e, e, part);
+      });
+      const double res = sqrt(ns_block_reduce<NS_SUM>(part, s_red, tid));  // barriers inside: sT complete
+      if (res != res) break;  // NaN: singular to working precision (or bad input)
+      if (!restarted && !(res < 0.7)) {  // the carried inverse is no contraction for this K: safe start instead
+        restarted = true;
+        o.restarts = 1;
+        restart();
+        continue;
+      }
+      // X <- 2 X - X T
+      tiles_product(bk, sX, sT, acc);
+      __syncthreads();  // every wave has finished reading the old X
+      tile_block_entries<NS_NBI, NS_NBJ>(bk, lane, [&](int i, int j, int c, int row, int col) {
+        sX[row * S + col] = 2.0 * sX[row * S + col] - acc[i][j][c];
+      });
+      __syncthreads();
+      if (res < 1e-6) {
+        o.status = 0;
+        break;
       }
     }
+    return o;
   }
 
-  int status = RT_WARN_SINGULAR;
-  bool restarted = !have_prev;
-  int n_iter = 0, n_restart = 0;
-  for (int it = 0; it < NS_MAX_ITER; ++it) {
-    ++n_iter;
-    // T = K X and the residual ||I - T||_F
-    double part = 0.0;
-    d4 acc[NBI][NBJ];
-    tiles_product(sK, sX, acc);
-#pragma unroll
-    for (int i = 0; i < NBI; ++i)
-#pragma unroll
-      for (int j = 0; j < NBJ; ++j)
-        if (i < bk.ni && j < bk.nj) {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            const int row = 16 * (bk.i0 + i) + l4 + 4 * c, col = 16 * (bk.j0 + j) + l15;
-            sT[row * S + col] = acc[i][j][c];
-            const double e = ((row == col) ? 1.0 : 0.0) - acc[i][j][c];
-            part = fma(e, e, part);
-          }
-        }
-    const double res = sqrt(ns_block_sum(part, s_red, tid));  // barriers inside: sT complete
-    if (res != res) break;  // NaN: singular to working precision (or bad input)
-    if (!restarted && !(res < 0.7)) {  // the carried inverse is no contraction for this K: safe start instead
-      restarted = true;
-      n_restart = 1;
-      restart();
-      continue;
-    }
-    // X <- 2 X - X T
-    tiles_product(sX, sT, acc);
-    __syncthreads();  // every wave has finished reading the old X
-#pragma unroll
-    for (int i = 0; i < NBI; ++i)
-#pragma unroll
-      for (int j = 0; j < NBJ; ++j)
-        if (i < bk.ni && j < bk.nj) {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            const int row = 16 * (bk.i0 + i) + l4 + 4 * c, col = 16 * (bk.j0 + j) + l15;
-            sX[row * S + col] = 2.0 * sX[row * S + col] - acc[i][j][c];
-          }
-        }
-    __syncthreads();
-    if (res < 1e-6) {
-      status = 0;
-      break;
-    }
-  }
-
-  if (tid == 0) {  // rt_last_sweep_stats
-    atomicAdd(reinterpret_cast<unsigned long long*>(&counters[RT_CNT_NS_ITER]), (unsigned long long)n_iter);
-    atomicAdd(reinterpret_cast<unsigned long long*>(&counters[RT_CNT_NS_RESTART]), (unsigned long long)n_restart);
-    atomicAdd(reinterpret_cast<unsigned long long*>(&counters[RT_CNT_SOLVES]), 1ull);
-  }
-  if (status != 0 && solved) {
-    // the refinement had already delivered the answer; only the refresh of X failed: start afresh next time
-    for (int i = wid; i < r; i += NS_THREADS / 64)
-      for (int j = lane; j < r; j += 64) Xb[i * r + j] = 0.0;
-    if (info && tid == 0) info[blockIdx.x] = 0;
-    if (adv.enabled) {
-      __syncthreads();
-      hsweep_advance_rows(adv, blockIdx.x, r, rhs, 1, s_vec[1], tid, NS_THREADS);
-    }
-    return;
-  }
-  if (status != 0) {
-    // The tracking gave up on this system (singular to working precision, or no contraction even from the safe
-    // start): pivoted LU right here, out of the copy of K this workgroup already holds, and the next call starts
-    // afresh.  (It used to be a second launch per step that found nothing to do in all but a handful of steps.)
-    for (int i = wid; i < r; i += NS_THREADS / 64)
-      for (int j = lane; j < r; j += 64) Xb[i * r + j] = 0.0;
-    if (tid == 0) atomicAdd(reinterpret_cast<unsigned long long*>(&counters[RT_CNT_LU_FALLBACK]), 1ull);
-    int lu_parts = NS_THREADS / r;
-    if (lu_parts > 8) lu_parts = 8;
-    __syncthreads();
-    const int sing = lu_solve_lds<NS_THREADS>(sK, S, s_vec[0], r, lu_parts, rb);
-    if (info && tid == 0) info[blockIdx.x] = sing ? RT_WARN_SINGULAR : 0;
-    if (adv.enabled) {
-      __syncthreads();
-      hsweep_advance_rows(adv, blockIdx.x, r, rhs, 1, s_vec[1], tid, NS_THREADS);
-    }
-    return;
-  }
-  if (!solved) {   // x = X b, one refinement step against K:  x += X (b - K x)
+  // x = X b, one refinement step against K:  x += X (b - K x); the answer goes to rb
+  __device__ __forceinline__ void solve_refined(double* rb) const {
     matvec(sX, s_vec[0], s_vec[1]);
     const double x = (tid < r) ? s_vec[1][tid] : 0.0;
     matvec(sK, s_vec[1], s_vec[2]);
@@ -549,28 +504,75 @@ __global__ __launch_bounds__(NS_THREADS) void newton_solve_kernel(const double* 
     matvec(sX, s_vec[2], s_vec[1]);
     if (tid < r) rb[tid] = x + s_vec[1][tid];
   }
-  if (wide_ok) {   // the refreshed inverse goes back the way it came: one 16-byte store per lane and row
-    const int j = 2 * lane;
-    d2 xv[10];
-#pragma unroll
-    for (int q = 0; q < 10; ++q) {
-      const int i = wid + 8 * q;
-      if (i < r && j < r) xv[q] = *reinterpret_cast<const d2*>(sX + i * S + j);
-    }
-#pragma unroll
-    for (int q = 0; q < 10; ++q) {
-      const int i = wid + 8 * q;
-      if (i < r && j < r) *reinterpret_cast<d2*>(Xb + i * r + j) = xv[q];
-    }
-  } else {
-    for (int i = wid; i < r; i += NS_THREADS / 64)
-      for (int j = lane; j < r; j += 64) Xb[i * r + j] = sX[i * S + j];
+
+  // The tracking gave up on this system (singular to working precision, or no contraction even from the safe start):
+  // pivoted LU right here, out of the copy of K this workgroup already holds.  Returns the info word.
+  __device__ __forceinline__ int lu_fallback(double* rb) const {
+    const int lu_parts = NS_THREADS / r > 8 ? 8 : NS_THREADS / r;
+    __syncthreads();
+    return lu_solve_lds<NS_THREADS>(sK, S, s_vec[0], r, lu_parts, rb) ? RT_WARN_SINGULAR : 0;
   }
-  if (info && tid == 0) info[blockIdx.x] = status;
-  if (adv.enabled) {  // the hyper-reduced sweep's end of step for this system
-    __syncthreads();  // rb is complete and visible in this workgroup
-    hsweep_advance_rows(adv, blockIdx.x, r, rhs, 1, s_vec[1], tid, NS_THREADS);
+
+  // The one end of every route: the sweep's counters (rt_last_sweep_stats), the carried inverse zeroed where the next
+  // call has to start afresh, the info word, and the sweep's end of step for system b (x is in rhs).
+  __device__ __forceinline__ void finish(NsRoute route, const NsOutcome& ns, int code, int b, double* Xb, double* rhs,
+                                         int* info, long* counters, const rt_advance& adv) const {
+    if (tid == 0) {
+      auto bump = [&](int slot, int by) { atomicAdd(reinterpret_cast<unsigned long long*>(&counters[slot]), (unsigned long long)by); };
+      if (route != NS_KEPT) {
+        bump(RT_CNT_NS_ITER, ns.iters);
+        bump(RT_CNT_NS_RESTART, ns.restarts);
+      }
+      bump(RT_CNT_SOLVES, 1);
+      if (route == NS_LU) bump(RT_CNT_LU_FALLBACK, 1);
+    }
+    if (route == NS_REFRESH_FAILED || route == NS_LU)
+      for (int i = wid; i < r; i += NS_THREADS / 64)
+        for (int j = lane; j < r; j += 64) Xb[i * r + j] = 0.0;
+    if (info && tid == 0) info[b] = code;
+    if (adv.enabled) {
+      __syncthreads();  // the answer is complete and visible in this workgroup
+      hsweep_advance_rows(adv, b, r, rhs, 1, s_vec[1], tid, NS_THREADS);
+    }
   }
+};
+
+__global__ __launch_bounds__(NS_THREADS) void newton_solve_kernel(
+    const double* __restrict__ K, double* __restrict__ Xinv, double* __restrict__ rhs, int r, int S, int have_prev,
+    int* __restrict__ info, const rt_step_rhs rq, long* counters, const rt_advance adv) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  __shared__ double s_red[NS_THREADS / 64];
+  __shared__ double s_vec[4][96];   // r <= 80 here (three padded r x r matrices in the dynamic part)
+  const int tr = (r + 15) / 16, rp = tr * 16, b = blockIdx.x;
+  const int tid = threadIdx.x, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const NsGroup g{sm, sm + (size_t)rp * S, sm + 2 * (size_t)rp * S, s_vec, s_red, r, rp, S, tid, tid & 63, wid};
+  const double* Kb = K + (size_t)b * r * r;
+  double* Xb = Xinv + (size_t)b * r * r;
+  double* rb = rhs + (size_t)b * r;
+  const double* Mb = rq.MN ? step_rhs_mn(rq, b, r) : nullptr;
+  const bool wide = (r == rp) && ((reinterpret_cast<size_t>(Kb) | reinterpret_cast<size_t>(Xb) | reinterpret_cast<size_t>(Mb)) & 15) == 0;
+
+  g.load(Kb, Xb, Mb, have_prev, wide);
+  g.right_hand_side(rq, b, rb);
+  if (!have_prev) g.restart();
+
+  // the carried inverse as a preconditioner first; X is refreshed when that took many steps, or did not get there
+  int used = 0;
+  const bool solved = have_prev && g.refine(used);
+  if (solved && tid < r) rb[tid] = g.s_vec[1][tid];
+
+  if (solved && used <= NS_REFRESH_AFTER) {   // nearly every step of a sweep ends here, so it leaves at once
+    g.finish(NS_KEPT, NsOutcome{0, 0, 0}, 0, b, Xb, rhs, info, counters, adv);
+    return;
+  }
+  const NsOutcome ns = g.newton_schulz(!have_prev);
+  const NsRoute route = ns.status == 0 ? NS_REFRESHED : solved ? NS_REFRESH_FAILED : NS_LU;
+  const int code = route == NS_LU ? g.lu_fallback(rb) : 0;
+  if (route == NS_REFRESHED) {
+    if (!solved) g.solve_refined(rb);
+    g.store_X(Xb, wide);
+  }   // NS_REFRESH_FAILED: the refinement had already delivered the answer
+  g.finish(route, ns, code, b, Xb, rhs, info, counters, adv);
 }
 
 }  // namespace
@@ -618,17 +620,15 @@ extern "C" int rt_dense_solve_multi(rt_ctx* ctx, const double* K, int64_t r, con
 // do not fit the LDS (r > 80): the caller uses rt_dense_solve_batched.  With `recipe` the kernel forms the
 // right-hand side itself (and leaves it in rhs) instead of reading it.
 int rt_newton_solve_batched(rt_ctx* ctx, const double* K, double* Xinv, double* rhs, int64_t r, int64_t B,
-                            int have_prev, int* info, const rt_newton_rhs* recipe, const rt_advance* advance) {
+                            int have_prev, int* info, const rt_step_rhs* recipe, const rt_advance* advance) {
   const int rp = (int)((r + 15) / 16) * 16;
   int S = rp;
   while (S % 4 != 2) ++S;  // 2 S == 4 (mod 8): the 16 rows of an A-operand read fall in distinct LDS banks
   const size_t lds = sizeof(double) * 3 * (size_t)rp * S;
   if (lds > 155 * 1024) return RT_ERR_UNSUPPORTED;  // + 3.1 KB of static LDS <= the CU's 160 KB
   RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&newton_solve_kernel), 155 * 1024));
-  rt_newton_rhs rq{};
-  if (recipe) rq = *recipe;
   hipLaunchKernelGGL(newton_solve_kernel, dim3((unsigned)B), dim3(NS_THREADS), lds, ctx->stream, K, Xinv, rhs, (int)r, S,
-                     have_prev, info, rq, ctx->dev_counters, advance ? *advance : rt_advance{});
+                     have_prev, info, recipe ? *recipe : rt_step_rhs{}, ctx->dev_counters, advance ? *advance : rt_advance{});
   RT_HIP_CHECK(ctx, hipGetLastError());
   return RT_OK;
 }

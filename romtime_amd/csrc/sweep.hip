@@ -12,9 +12,6 @@
 #include "common.h"
 #include "sweep_step.h"
 
-typedef double xd2 __attribute__((ext_vector_type(2)));
-typedef double xd4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 // The expansion of the hyper-reduced step,  C (R x N) = G (R x K) Z (K x N)  with R <= 64 rows (K_N and M_N of all
@@ -39,8 +36,8 @@ __global__ __launch_bounds__(EX_THREADS) void expansion_kernel(const double* __r
   const long n0 = (long)blockIdx.x * 32;
   // four independent accumulator chains per wave (two column tiles x the parity of the k-step): with one wave per SIMD
   // nothing else hides the latency of an MFMA that waits for the previous one into the same accumulator
-  xd4 acc[2][2] = {{xd4{0, 0, 0, 0}, xd4{0, 0, 0, 0}}, {xd4{0, 0, 0, 0}, xd4{0, 0, 0, 0}}};
-  xd2 ra[EX_LA], rb[EX_LB];
+  d4 acc[2][2] = {{d4{0, 0, 0, 0}, d4{0, 0, 0, 0}}, {d4{0, 0, 0, 0}, d4{0, 0, 0, 0}}};
+  d2 ra[EX_LA], rb[EX_LB];
   // Branch-free loads: every load goes to a clamped, aligned address and is zeroed afterwards where it was out of range
   // (even K, N and leading dimensions: the host checks) - a predicate per load makes the compiler wait for each load
   // where it is issued.
@@ -51,8 +48,8 @@ __global__ __launch_bounds__(EX_THREADS) void expansion_kernel(const double* __r
       const int k = k0 + kk;
       const bool ok = row < R && k < K;
       const long off = (long)(row < R ? row : R - 1) * ldg + (k < K ? k : K - 2);
-      const xd2 v = *reinterpret_cast<const xd2*>(G + off);
-      ra[i] = ok ? v : xd2{0.0, 0.0};
+      const d2 v = *reinterpret_cast<const d2*>(G + off);
+      ra[i] = ok ? v : d2{0.0, 0.0};
     }
 #pragma unroll
     for (int i = 0; i < EX_LB; ++i) {
@@ -60,20 +57,20 @@ __global__ __launch_bounds__(EX_THREADS) void expansion_kernel(const double* __r
       const int k = k0 + kk;
       const bool ok = k < K && n0 + j < N;
       const long off = (long)(k < K ? k : K - 1) * ldz + (n0 + j < N ? n0 + j : N - 2);
-      const xd2 v = *reinterpret_cast<const xd2*>(Z + off);
-      rb[i] = ok ? v : xd2{0.0, 0.0};
+      const d2 v = *reinterpret_cast<const d2*>(Z + off);
+      rb[i] = ok ? v : d2{0.0, 0.0};
     }
   };
   auto commit = [&]() {
 #pragma unroll
     for (int i = 0; i < EX_LA; ++i) {
       const int q = tid + EX_THREADS * i, row = q / (EX_KP / 2), kk = 2 * (q % (EX_KP / 2));
-      *reinterpret_cast<xd2*>(&sA[row * EX_SA + kk]) = ra[i];
+      *reinterpret_cast<d2*>(&sA[row * EX_SA + kk]) = ra[i];
     }
 #pragma unroll
     for (int i = 0; i < EX_LB; ++i) {
       const int q = tid + EX_THREADS * i, kk = q / 16, j = 2 * (q % 16);
-      *reinterpret_cast<xd2*>(&sB[kk * EX_SB + j]) = rb[i];
+      *reinterpret_cast<d2*>(&sB[kk * EX_SB + j]) = rb[i];
     }
   };
   const double* fa = sA + (16 * wid + l15) * EX_SA + l4;   // A operand: row 16 w + l15, k = 4 k4 + l4
@@ -186,22 +183,13 @@ __global__ void hsweep_advance_kernel(const double* __restrict__ x, int do_store
 
 __global__ void hsweep_count_kernel(long* ctr) { *ctr += 1; }
 
-// rhs[b] = M_N[b] (c0 u_n[b] + c1 u_nm1[b]) + dt Zf^T Ff[b]: the recipe the solver kernels evaluate in their own
-// prologue, as a kernel for the r > 80 route; one thread per row, every sum in sequence
-__global__ void step_rhs_kernel(const rt_newton_rhs rq, int r, double* __restrict__ rhs) {
+// The recipe the solver kernels evaluate in their own prologue (sweep_step.h) as a kernel, for the r > 80 route
+__global__ void step_rhs_kernel(const rt_step_rhs rq, int r, double* __restrict__ rhs) {
   extern __shared__ double su[];
   const int b = blockIdx.x, t = threadIdx.x;
-  if (t < r) su[t] = rq.c0 * rq.un[(long)b * r + t] + rq.c1 * rq.unm1[(long)b * r + t];
+  if (t < r) su[t] = step_rhs_state(rq, b, r, t);
   __syncthreads();
-  if (t < r) {
-    const double* M = rq.MN + (long)b * (rq.mn_stride < 0 ? (long)r * r : rq.mn_stride) + (long)t * r;
-    const double* Ff = (rq.ctr ? rq.Ff + *rq.ctr * rq.ff_stride : rq.Ff) + (long)b * rq.mf;
-    double acc = 0.0;
-    for (int j = 0; j < r; ++j) acc = fma(M[j], su[j], acc);
-    double f = 0.0;
-    for (int e = 0; e < rq.mf; ++e) f = fma(Ff[e], rq.Zf[(long)e * r + t], f);
-    rhs[(long)b * r + t] = fma(rq.dt, f, acc);
-  }
+  if (t < r) rhs[(long)b * r + t] = step_rhs_row(rq, step_rhs_mn(rq, b, r), step_rhs_forcing_rows(rq, b), r, t, su);
 }
 
 // The reduced solver's buffers, the same in both sweeps
@@ -218,24 +206,17 @@ struct StepWork {
 // Takes the composite arena ONCE, for the solver's buffers and `extra` bytes of the sweep's own (*extra_base, 256-B
 // aligned), and zeroes the state and the sweep's counters on the ctx stream.
 int step_work_get(rt_ctx* ctx, long r, long B, long kn_mats, size_t extra, StepWork* w, char** extra_base) {
-  size_t off = 0;
-  auto take = [&off](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+  rt_carver a;
   const bool gmres = ctx->reduced_solver == RT_SOLVER_GMRES;
-  const size_t oKN = take(sizeof(double) * kn_mats * r * r), oRhs = take(sizeof(double) * B * r),
-               oUn = take(sizeof(double) * B * r), oUm = take(sizeof(double) * B * r),
-               oXi = take(sizeof(double) * B * r * r), oInfo = take(sizeof(int) * B),
-               oGw = take(gmres ? rt_gmres_work_bytes(r, B, &ctx->gmres_opts) : 0);
+  const size_t oKN = a.add(sizeof(double) * kn_mats * r * r), oRhs = a.add(sizeof(double) * B * r),
+               oUn = a.add(sizeof(double) * B * r), oUm = a.add(sizeof(double) * B * r),
+               oXi = a.add(sizeof(double) * B * r * r), oInfo = a.add(sizeof(int) * B),
+               oGw = a.add(gmres ? rt_gmres_work_bytes(r, B, &ctx->gmres_opts) : 0);
   void* base = nullptr;
-  RT_TRY(rt_scratch2(ctx, off + extra, &base));
-  char* b8 = static_cast<char*>(base);
-  w->KN = reinterpret_cast<double*>(b8 + oKN);
-  w->rhs = reinterpret_cast<double*>(b8 + oRhs);
-  w->un = reinterpret_cast<double*>(b8 + oUn);
-  w->unm1 = reinterpret_cast<double*>(b8 + oUm);
-  w->Xinv = reinterpret_cast<double*>(b8 + oXi);
-  w->info = reinterpret_cast<int*>(b8 + oInfo);
-  w->gwork = reinterpret_cast<double*>(b8 + oGw);
-  *extra_base = b8 + off;
+  RT_TRY(rt_scratch2(ctx, a.total() + extra, &base));
+  *w = StepWork{a.at<double>(base, oKN), a.at<double>(base, oRhs), a.at<double>(base, oUn), a.at<double>(base, oUm),
+                a.at<double>(base, oXi), a.at<int>(base, oInfo), a.at<double>(base, oGw)};
+  *extra_base = a.at<char>(base, a.total());
   RT_HIP_CHECK(ctx, hipMemsetAsync(w->un, 0, sizeof(double) * B * r, ctx->stream));
   RT_HIP_CHECK(ctx, hipMemsetAsync(w->unm1, 0, sizeof(double) * B * r, ctx->stream));
   RT_HIP_CHECK(ctx, hipMemsetAsync(ctx->dev_counters + RT_CNT_NS_ITER, 0, sizeof(long) * 6, ctx->stream));  // stats + GMRES counters
@@ -246,7 +227,7 @@ int step_work_get(rt_ctx* ctx, long r, long B, long kn_mats, size_t extra, StepW
 // the solver kernel forms the right-hand side, the tracked solve falls back to its LU by itself where the tracking
 // fails, and the kernel's tail closes the step.  r > 80, where the tracked solve's three matrices do not fit the LDS:
 // three launches - right-hand side, plain pivoted LU, step close.
-int sweep_step_solve(rt_ctx* ctx, const StepWork& w, long r, long B, int have_prev, const rt_newton_rhs& rq,
+int sweep_step_solve(rt_ctx* ctx, const StepWork& w, long r, long B, int have_prev, const rt_step_rhs& rq,
                      const rt_advance& adv) {
   const int rc = ctx->reduced_solver == RT_SOLVER_GMRES
                      ? rt_gmres_launch(ctx, w.KN, nullptr, w.rhs, r, B, &ctx->gmres_opts, nullptr, nullptr, w.gwork, &rq, &adv, true)
@@ -273,23 +254,18 @@ extern "C" int rt_rom_bdf_sweep(rt_ctx* ctx, const rt_sweep_desc* d, double* uN_
   hipStream_t st = ctx->stream;
 
   // workspace (composite arena): the solver's buffers, then this sweep's own
-  size_t off = 0;
-  auto take = [&off](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-  const size_t oRow = take(sizeof(int) * nnz), oMN = take(sizeof(double) * r * r), oFN = take(sizeof(double) * (F ? F : 1) * r),
-               oUh = take(sizeof(double) * B * N), oUp = take(sizeof(double) * B * N), oXT = take(sizeof(double) * r * B),
-               oKv = take(sizeof(double) * B * nnz), oTab = take(rt_project_stage_table_bytes(N));
+  rt_carver a;
+  const size_t oRow = a.add(sizeof(int) * nnz), oMN = a.add(sizeof(double) * r * r), oFN = a.add(sizeof(double) * (F ? F : 1) * r),
+               oUh = a.add(sizeof(double) * B * N), oUp = a.add(sizeof(double) * B * N), oXT = a.add(sizeof(double) * r * B),
+               oKv = a.add(sizeof(double) * B * nnz), oTab = a.add(rt_project_stage_table_bytes(N));
   StepWork w;
   char* b8 = nullptr;
-  int rc = step_work_get(ctx, r, B, B, off, &w, &b8);
+  int rc = step_work_get(ctx, r, B, B, a.total(), &w, &b8);
   if (rc != RT_OK) return rc;
-  int* row_of = reinterpret_cast<int*>(b8 + oRow);
-  double* MN = reinterpret_cast<double*>(b8 + oMN);
-  double* fN = reinterpret_cast<double*>(b8 + oFN);
-  double* uh = reinterpret_cast<double*>(b8 + oUh);
-  double* uhp = reinterpret_cast<double*>(b8 + oUp);
-  double* xT = reinterpret_cast<double*>(b8 + oXT);
-  double* kval = reinterpret_cast<double*>(b8 + oKv);
-  void* stage_table = b8 + oTab;  // per-pattern stage records of the fused projection, built once per sweep
+  int* row_of = a.at<int>(b8, oRow);
+  double *MN = a.at<double>(b8, oMN), *fN = a.at<double>(b8, oFN), *uh = a.at<double>(b8, oUh), *uhp = a.at<double>(b8, oUp),
+         *xT = a.at<double>(b8, oXT), *kval = a.at<double>(b8, oKv);
+  void* stage_table = a.at<void>(b8, oTab);  // per-pattern stage records of the fused projection, built once per sweep
 
   RT_HIP_CHECK(ctx, hipMemsetAsync(uh, 0, sizeof(double) * B * N, st));
   RT_HIP_CHECK(ctx, hipMemsetAsync(uhp, 0, sizeof(double) * B * N, st));
@@ -327,7 +303,7 @@ extern "C" int rt_rom_bdf_sweep(rt_ctx* ctx, const rt_sweep_desc* d, double* uN_
     // reference: step 0 of a BDF2 run uses M_N (2 u^0 - u^{-1}/2) with both zero (rom.py:451-458,921-924)
     // consecutive K_N differ by O(dt): the tracked solve refreshes the carried inverse on the matrix cores.  The step
     // closes with u^n, u^{n-1}, the trajectory row and u^n transposed for the lift.
-    rt_newton_rhs rq{MN, w.un, w.unm1, c0, c1, d->dt, F ? d->rhs_coef + step * B * F : nullptr, fN, F};
+    rt_step_rhs rq{MN, w.un, w.unm1, c0, c1, d->dt, F ? d->rhs_coef + step * B * F : nullptr, fN, F};
     rq.mn_stride = 0;
     rt_advance close{};
     close.un = w.un; close.unm1 = w.unm1; close.out = uN_out; close.step_done = step; close.nt = nt;
@@ -388,7 +364,7 @@ extern "C" int rt_hrom_bdf_sweep(rt_ctx* ctx, const rt_hsweep_desc* d, double* u
   const double c0 = d->bdf2 ? 2.0 : 1.0, c1 = d->bdf2 ? -0.5 : 0.0;
   // One step: [K_N; M_N][b][ij] = sum_e G[b][e] Z[e][ij] (2 B rows), then the solve, which forms the right-hand side
   // and closes the step (state, trajectory, next rows of G) - two launches for r <= 80
-  auto step_body = [&](const rt_newton_rhs& rq, const rt_advance& adv, int have_prev) {
+  auto step_body = [&](const rt_step_rhs& rq, const rt_advance& adv, int have_prev) {
     int rc2 = rt_expansion_gemm(ctx, G, M, d->Z, rr, KN, rr, 2 * B, M, rr);
     if (rc2 == RT_ERR_UNSUPPORTED) rc2 = rt_gemm_strided(ctx, G, 1, M, d->Z, rr, 1, M, 2 * B, rr, KN, rr, 1, false, false);
     return rc2 != RT_OK ? rc2 : sweep_step_solve(ctx, w, r, B, have_prev, rq, adv);
@@ -419,7 +395,7 @@ extern "C" int rt_hrom_bdf_sweep(rt_ctx* ctx, const rt_hsweep_desc* d, double* u
       ctx->stream = gs;
       st = gs;
       RT_HIP_CHECK(ctx, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-      rt_newton_rhs rq{MN, w.un, w.unm1, c0, c1, d->dt, mf ? d->F_rhs : nullptr, d->Zf, (int)mf};
+      rt_step_rhs rq{MN, w.un, w.unm1, c0, c1, d->dt, mf ? d->F_rhs : nullptr, d->Zf, (int)mf};
       rq.ctr = ctr;
       rq.ff_stride = B * mf;
       rt_advance ga = advance_args(1);   // table bases + device counter: the replayed launches cannot carry the step
@@ -449,7 +425,7 @@ extern "C" int rt_hrom_bdf_sweep(rt_ctx* ctx, const rt_hsweep_desc* d, double* u
       RT_HIP_CHECK(ctx, le);
       break;
     }
-    const rt_newton_rhs rq{MN, w.un, w.unm1, c0, c1, d->dt, mf ? d->F_rhs + step * B * mf : nullptr, d->Zf, (int)mf};
+    const rt_step_rhs rq{MN, w.un, w.unm1, c0, c1, d->dt, mf ? d->F_rhs + step * B * mf : nullptr, d->Zf, (int)mf};
     rc = step_body(rq, advance_args(step + 1), step > 0 ? 1 : 0);
     if (rc != RT_OK) return rc;
   }

@@ -1,14 +1,15 @@
 // One step of an online sweep, described by value for the kernels that run it: how the right-hand side is formed
-// (rt_newton_rhs) and how the step is closed once the systems are solved (rt_advance: state, previous state,
+// (rt_step_rhs) and how the step is closed once the systems are solved (rt_advance: state, previous state,
 // trajectory row, the coefficient rows of the next step, the state transposed for the direct sweep's lift).
-// hsweep_advance_rows closes the step for ONE parameter point.  It runs as the tail of newton_solve_kernel (solve.hip)
-// and of gmres_kernel (gmres.hip), so that a step is expansion + solve instead of four launches (the host of the pool's
-// boxes sustains only about one launch per 20 us), and in the stand-alone hsweep_advance_kernel (sweep.hip) before the
-// first step and after the plain LU of the r > 80 route.
+// The recipe's evaluation lives here too (step_rhs_*), for the three kernels that form a right-hand side:
+// newton_solve_kernel (solve.hip), gmres_kernel (gmres.hip), step_rhs_kernel (sweep.hip).  hsweep_advance_rows closes
+// the step for ONE parameter point.  It runs as the tail of newton_solve_kernel and of gmres_kernel, so that a step is
+// expansion + solve instead of four launches (the host of the pool's boxes sustains only about one launch per 20 us),
+// and in the stand-alone hsweep_advance_kernel (sweep.hip) before the first step and after the plain LU of r > 80.
 #pragma once
 
 // b = M_N (c0 u^n + c1 u^{n-1}) + dt Zf^T F_rhs, per system; MN == nullptr: rhs is given
-struct rt_newton_rhs {
+struct rt_step_rhs {
   const double* MN;    // B x r x r
   const double* un;    // B x r
   const double* unm1;  // B x r
@@ -20,6 +21,35 @@ struct rt_newton_rhs {
   const long* ctr = nullptr;  // device step counter: Ff is the table base and the step's rows start at *ctr * ff_stride
   long ff_stride = 0;         // (graph replay of a sweep: the launch parameters cannot carry the step)
 };
+
+// The pieces of the recipe for system b and entry i: M_N of the system, its forcing rows of this step (nullptr without
+// forcing terms), the state mix, the forcing sum.  Every sum is a chain of fma in index order.
+__device__ __forceinline__ const double* step_rhs_mn(const rt_step_rhs& q, long b, int r) {
+  return q.MN + b * (q.mn_stride < 0 ? (long)r * r : q.mn_stride);
+}
+__device__ __forceinline__ const double* step_rhs_forcing_rows(const rt_step_rhs& q, long b) {
+  return q.mf ? (q.ctr ? q.Ff + *q.ctr * q.ff_stride : q.Ff) + b * q.mf : nullptr;
+}
+// The fma is spelled out so that the result does not depend on the contraction mode of the file that includes this
+// header (gmres.hip turns contraction off).  The sweeps pass (c0, c1) = (2, -0.5) or (1, 0): both products are exact,
+// so one rounding either way, and the same bits as a separate multiply and add.
+__device__ __forceinline__ double step_rhs_state(const rt_step_rhs& q, long b, int r, int i) {
+  return fma(q.c0, q.un[b * r + i], q.c1 * q.unm1[b * r + i]);
+}
+__device__ __forceinline__ double step_rhs_forcing(const rt_step_rhs& q, const double* Ff, int r, int i) {
+  double f = 0.0;
+  for (int e = 0; e < q.mf; ++e) f = fma(Ff[e], q.Zf[(long)e * r + i], f);
+  return f;
+}
+// Row i of b with the system's M_N (Mb) read from global memory and the state mix s (r values) from LDS, one thread per
+// row.  Mb and Ff are the two bases above, which a caller with several rows per thread takes once.
+__device__ __forceinline__ double step_rhs_row(const rt_step_rhs& q, const double* Mb, const double* Ff, int r, int i,
+                                               const double* s) {
+  const double* Mrow = Mb + (long)i * r;
+  double acc = 0.0;
+  for (int j = 0; j < r; ++j) acc = fma(Mrow[j], s[j], acc);
+  return fma(q.dt, step_rhs_forcing(q, Ff, r, i), acc);
+}
 
 struct rt_advance {
   double* un;            // B x r   u^n            (updated)

@@ -886,15 +886,13 @@ struct EigArena {
   double *V, *own, *tau, *d, *e;
   int* flags;
   int carve(rt_ctx* ctx, int64_t n, size_t own_bytes) {
-    size_t off = 0;
-    auto take = [&off](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-    const size_t oV = take(sizeof(double) * n * n), oO = take(own_bytes), oT = take(sizeof(double) * n),
-                 oD = take(sizeof(double) * n), oE = take(sizeof(double) * n), oF = take(sizeof(int) * (SLOT0 + TW_LARGE));
-    RT_TRY(rt_scratch2(ctx, off, &base));
-    char* b8 = static_cast<char*>(base);
-    V = reinterpret_cast<double*>(b8 + oV); own = reinterpret_cast<double*>(b8 + oO);
-    tau = reinterpret_cast<double*>(b8 + oT); d = reinterpret_cast<double*>(b8 + oD);
-    e = reinterpret_cast<double*>(b8 + oE); flags = reinterpret_cast<int*>(b8 + oF);
+    rt_carver a;
+    const size_t oV = a.add(sizeof(double) * n * n), oO = a.add(own_bytes), oT = a.add(sizeof(double) * n),
+                 oD = a.add(sizeof(double) * n), oE = a.add(sizeof(double) * n), oF = a.add(sizeof(int) * (SLOT0 + TW_LARGE));
+    RT_TRY(rt_scratch2(ctx, a.total(), &base));
+    V = a.at<double>(base, oV); own = a.at<double>(base, oO);
+    tau = a.at<double>(base, oT); d = a.at<double>(base, oD);
+    e = a.at<double>(base, oE); flags = a.at<int>(base, oF);
     return RT_OK;
   }
   void publish(rt_ctx* ctx, int64_t n) const {

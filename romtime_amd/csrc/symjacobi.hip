@@ -200,17 +200,15 @@ extern "C" int rt_sym_jacobi_eigh(rt_ctx* ctx, const double* A, int64_t n, doubl
     return RT_ERR_UNSUPPORTED;
   }
   // composite arena: work copy (x2) | rotations W | perm | counter
-  size_t off = 0;
-  auto take = [&off](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+  rt_carver a;
   const size_t nn = sizeof(double) * (size_t)n * n;
-  const size_t o0 = take(nn), o1 = take(nn), oW = take(nn), oP = take(sizeof(int) * n), oC = take(sizeof(int));
+  const size_t o0 = a.add(nn), o1 = a.add(nn), oW = a.add(nn), oP = a.add(sizeof(int) * n), oC = a.add(sizeof(int));
   void* base = nullptr;
-  RT_TRY(rt_scratch2(ctx, off, &base));
-  char* b8 = static_cast<char*>(base);
-  double* work[2] = {reinterpret_cast<double*>(b8 + o0), reinterpret_cast<double*>(b8 + o1)};
-  double* Ww = reinterpret_cast<double*>(b8 + oW);
-  int* perm = reinterpret_cast<int*>(b8 + oP);
-  int* counter = reinterpret_cast<int*>(b8 + oC);
+  RT_TRY(rt_scratch2(ctx, a.total(), &base));
+  double* work[2] = {a.at<double>(base, o0), a.at<double>(base, o1)};
+  double* Ww = a.at<double>(base, oW);
+  int* perm = a.at<int>(base, oP);
+  int* counter = a.at<int>(base, oC);
   hipStream_t st = ctx->stream;
   const unsigned cells = (unsigned)(((long)n * n + JAC_T - 1) / JAC_T);
   RT_HIP_CHECK(ctx, hipMemsetAsync(perm, 0xff, sizeof(int) * n, st));

@@ -24,9 +24,6 @@
 // profiles/r03_tallskinny_ab.txt.
 #include "common.h"
 
-typedef double d2 __attribute__((ext_vector_type(2)));
-typedef double d4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 constexpr int TS_THREADS = 256;
@@ -234,13 +231,7 @@ int rt_tallskinny(rt_ctx* ctx, const double* X, int64_t ldx, const double* T, in
   const int rb = (nt <= 4 && N >= 128L * 4 * ctx->num_cus) ? 2 : 1;
   const int bm = 64 * rb;
   const unsigned grid = (unsigned)((N + bm - 1) / bm);
-  if (ctx->profile) {
-    if (!ctx->ev0) {
-      RT_HIP_CHECK(ctx, hipEventCreate(&ctx->ev0));
-      RT_HIP_CHECK(ctx, hipEventCreate(&ctx->ev1));
-    }
-    RT_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  }
+  RT_TRY(rt_profile_begin(ctx));
   // 1 <= k % 16 <= 12: the remainder goes through ceil((k % 16) / 4) four-block instructions; otherwise whole tiles only
   const int c = (int)(k % 16);
   const int kf = (c == 0 || c >= 13) ? nt : nt - 1, g = (c == 0 || c >= 13) ? 0 : (c + 3) / 4;
@@ -254,10 +245,7 @@ int rt_tallskinny(rt_ctx* ctx, const double* X, int64_t ldx, const double* T, in
 #undef TS_ROW
 #undef TS_CASE
   RT_HIP_CHECK(ctx, hipGetLastError());
-  if (ctx->profile) {
-    RT_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    ctx->ev_valid = true;
-  }
+  RT_TRY(rt_profile_end(ctx));
   ctx->last_grid = grid; ctx->last_splits = 1; ctx->last_tile = bm * 1000 + 16 * nt;
   return RT_OK;
 }

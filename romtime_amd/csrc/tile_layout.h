@@ -1,6 +1,7 @@
 // Which 16 x 16 output tiles of an r x r product each of the 8 waves of a workgroup owns (project_fused.hip,
 // solve.hip).
 #pragma once
+#include <type_traits>
 
 // Wave w owns one rectangular block (rows i0..i0+ni-1 x columns j0..j0+nj-1 of the tile grid).
 // Waves w and w + 4 share a SIMD; the layouts balance MFMA work per SIMD as far as the tile count allows
@@ -48,4 +49,35 @@ __host__ __device__ inline Blk tile_block(int tr, int wave) {
     case 7: return Layout<7>::blk[wave];
     default: return Layout<8>::blk[wave];
   }
+}
+
+// Host side: f(std::integral_constant<int, TR>{}) for the run-time tr = 1..8, so that f can name a template on TR.
+template <class F>
+auto tile_rows_dispatch(int tr, F&& f) {
+  switch (tr) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+    default: return f(std::integral_constant<int, 8>{});
+  }
+}
+
+// For every entry this lane holds of its wave's block after a product on the 16x16x4 FP64 matrix cores with one
+// accumulator (four doubles) per tile, at most NBI x NBJ tiles: f(i, j, c, row, col), where acc[i][j][c] is entry
+// (row, col) of the whole matrix.  Tile (i, j) of the block; lane l holds rows (l >> 4) + 4 c of column l & 15.
+template <int NBI, int NBJ, class F>
+__device__ __forceinline__ void tile_block_entries(const Blk& bk, int lane, F&& f) {
+  const int l15 = lane & 15, l4 = lane >> 4;
+#pragma unroll
+  for (int i = 0; i < NBI; ++i)
+#pragma unroll
+    for (int j = 0; j < NBJ; ++j)
+      if (i < bk.ni && j < bk.nj) {   // wave-uniform
+#pragma unroll
+        for (int c = 0; c < 4; ++c) f(i, j, c, 16 * (bk.i0 + i) + l4 + 4 * c, 16 * (bk.j0 + j) + l15);
+      }
 }

@@ -27,9 +27,6 @@
 // (u - l)^2 and the sums are separate IEEE operations, as NumPy's are: exact data then gives NumPy's bits
 #pragma clang fp contract(off)
 
-typedef double d2 __attribute__((ext_vector_type(2)));
-typedef double d4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 constexpr int TE_THREADS = 256;

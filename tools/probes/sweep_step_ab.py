@@ -1,5 +1,5 @@
 """Both online sweeps on a fixed seeded list of small cases that between them take every route of the reduced step:
-tracked solve (scalar and 16-byte loads), its in-kernel LU fallback, the r > 80 route (right-hand-side kernel, plain LU,
+tracked solve (scalar and 16-byte loads, one tile to 25), its in-kernel LU fallback, the r > 80 route (right-hand-side kernel, plain LU,
 step close), GMRES mode, eager and graph replay, BDF1 and BDF2, with and without right-hand-side terms.  Prints per case
 the SHA-256 of the returned trajectory's bytes, Context.sweep_stats() and the two GMRES counters; a refactor of the step
 must leave every row as it was.  Runs against the checkout it is started from (--root), so the same file serves the
@@ -98,6 +98,12 @@ report("hrom_r96_gmres", lambda: hrom_bdf_sweep(*synthetic(96, 5, 2, seed=7), 1e
 report("direct_r24_gmres", lambda: rom_bdf_sweep(*direct(24, 40, True), bdf2=True, solver="gmres"))
 report("direct_r24_no_rhs", lambda: rom_bdf_sweep(*direct(24, 40, True, with_rhs=False), bdf2=True))
 report("direct_r96_no_rhs", lambda: rom_bdf_sweep(*direct(96, 6, True, with_rhs=False), bdf2=True))
+# the tracked solve's 16-byte loads with the direct sweep's one shared M_N, its smallest (one tile) and largest (25 tiles)
+# sizes, and GMRES with the Krylov basis in the global work area (r > 121 at restart 20)
+report("direct_r32_bdf2", lambda: rom_bdf_sweep(*direct(32, 12, True), bdf2=True))
+report("hrom_r16_bdf2", lambda: hrom_bdf_sweep(*synthetic(16, 9, 3, seed=11), 1e-2, bdf2=True))
+report("hrom_r80_bdf2", lambda: hrom_bdf_sweep(*synthetic(80, 5, 2, seed=13), 1e-2, bdf2=True))
+report("hrom_r128_gmres", lambda: hrom_bdf_sweep(*synthetic(128, 3, 2, seed=17), 1e-2, bdf2=True, solver="gmres"))
 
 if args.time:
     nt = args.time_steps
