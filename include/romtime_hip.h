@@ -314,6 +314,36 @@ int rt_trajectory_errors(rt_ctx* ctx, const double* B, int64_t ldb, const double
                          const double* U, int64_t ldu, int u_layout, int64_t stride_u, int64_t N, int64_t k, int64_t nt,
                          int64_t n_traj, double* err, double* ref);
 
+/* ---- physical outputs of whole trajectories: the mass  int rho(u) dx  on the moving mesh per time step
+ *      (compute_mass_conservation with compute_rho / compute_p, fom/nonlinear.py:601-683; the third block of
+ *      HyperReducedPiston._evaluate, hrom.py:586-621) ---- */
+#define RT_FN_POWER 0   /* f(z) = (c0 + c1 z)^p, par = {c0, c1, p} (host) */
+/* out[j][t] = scale[j][t] * sum_i w_i f(E_i . a_j[t]) for n_traj trajectories and nt steps each, since version 370; the
+ * lifted trajectory E a is never stored.  E: n_pts x k row-major (lde >= k), k <= 128 (RT_ERR_UNSUPPORTED beyond), 8-byte
+ * aligned: the basis evaluated at the quadrature points.  w: n_pts DEVICE weights, NULL = 1.  A: coefficients laid out
+ * exactly as for rt_trajectory_errors (the uN_out of the sweeps goes in unchanged).  scale: n_traj x nt DEVICE factors,
+ * NULL = 1 (the domain length L(mu_j, t) of the moving mesh).  out: n_traj x nt DEVICE.  fn selects f and par (HOST) holds
+ * its parameters; RT_FN_POWER is the only one.  Null E, A, par or out, sizes < 1, an unknown fn and lde or lda < k return
+ * RT_ERR_ARG.
+ *   - The base is b = fma(c1, z, c0).  Where p equals an integer in 1 .. 8 exactly, f is repeated multiplication in one
+ *     association - b2 = b b, b4 = b2 b2, then b, b2, b2 b, b4, b4 b, b4 b2, (b4 b2) b, b4 b4 - so exact data gives exact
+ *     bits.  Every other p goes through pow: a negative base with a non-integer p gives NaN in that step's output, and in
+ *     that step's output only.
+ *   - Rows past n_pts are predicated out of the sum, not multiplied by a zero weight: with c0 = 0 and p < 0 a padded row
+ *     evaluates f(0) = inf, and inf * 0 would poison a sum that is finite.
+ *   - No floating-point atomics: partial sums are written as [trajectory][row slice][step] (ctx leaf arena) and a finish
+ *     kernel adds the slices in order and applies scale.  The slicing depends on n_pts, nt and the ctx's CU count only, so
+ *     a trajectory's bits depend neither on n_traj nor on its place in the batch.
+ *   - rt_last_launch_info: [0] workgroups, [1] row slices, [2] tile 32 rows x 64 steps, as rt_trajectory_errors. */
+int rt_trajectory_integrals(rt_ctx* ctx, const double* E, int64_t lde, const double* w, const double* A, int64_t lda,
+                            int64_t stride_a, const double* scale, int64_t n_pts, int64_t k, int64_t nt, int64_t n_traj,
+                            int fn, const double* par, double* out);
+/* The argument checks and the launch plan of rt_trajectory_integrals for a ctx of num_cus CUs - host logic only, no GPU
+ * and no pointer is followed: the same return code, and on RT_OK info3 (may be NULL) as rt_last_launch_info reports it. */
+int rt_trajectory_integrals_plan_info(int num_cus, const double* E, int64_t lde, const double* w, const double* A, int64_t lda,
+                                      int64_t stride_a, const double* scale, int64_t n_pts, int64_t k, int64_t nt,
+                                      int64_t n_traj, int fn, const double* par, const double* out, int64_t* info3);
+
 /* ---- closed-form local assembly of the 1-D P1 operators at (M)DEIM entries (the step before the path) ----------
  * What ``assemble(mu, t, entries=dofs[, u_n])`` returns for the reference's 1-D problems (fom/base.py:523-599 per-entry
  * assembly of the forms in fom/nonlinear.py:374-494; closed forms as in testing/mock.py:30-85), for n_states states at

@@ -21,6 +21,10 @@ ProblemType = _ns("ProblemType", "which model a quantity belongs to", **_PROBLEM
 Errors = _ns("Errors", "keys of the per-parameter error payloads the driver writes (conventions.py:36-44)", **_PROBLEMS,
              SACRIFICIAL="sacrificial", ESTIMATOR="estimator", AVERAGE_ROM="rom_average",
              AVERAGE_ESTIMATOR="estimator_average", AVERAGE_SACRIFICIAL="srom_average")
+MassConservation = _ns("MassConservation", "keys of the mass-conservation payload (fom/nonlinear.py:675-681)", WHICH="which",
+                      TIMESTEPS="timesteps", MASS="mass", MASS_CHANGE="mass_change", OUTFLOW="outflow")
+ProbeLocations = _ns("ProbeLocations", "names of the three probes of the piston problem", OUTFLOW="outflow",
+                     MIDDLE="halfway", PISTON="piston")
 Stage = _ns("Stage", "phase of the reduction workflow", OFFLINE="offline", VALIDATION="validation", ONLINE="online")
 BDF = _ns("BDF", "time scheme order, as the FOM's BDF_SCHEME attribute spells it", ONE="1", TWO="2")
 EmpiricalInterpolation = _ns("EmpiricalInterpolation", "hyper-reductor kinds", DEIM="DEIM", MDEIM="MDEIM",

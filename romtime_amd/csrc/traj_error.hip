@@ -6,7 +6,8 @@
 // The lifted trajectory is a GEMM N x nt x k (k <= 128) whose output is only ever subtracted from U, squared and summed
 // down the rows, so it never leaves the accumulators.  A workgroup (4 waves) owns 64 steps and walks down a slice of
 // rows in stages of 32: the 64 x k coefficient block stays in LDS, the 32 x k stages of B go global -> registers -> LDS
-// with the next stage in flight while the current one is multiplied (tallskinny.hip's scheme), each wave multiplies one
+// with the next stage in flight while the current one is multiplied (tallskinny.hip's scheme; the loader is
+// traj_stage.h, shared with traj_output.hip), each wave multiplies one
 // 16-row block by two 16-step tiles on the f64 matrix cores, loads its 8 words of the U tile straight into the
 // accumulator layout at the top of the stage (they arrive under the MFMAs), and folds (u - l)^2 into per-lane column
 // sums that stay in registers until the slice is done.  An FP64 MFMA blocks the VALU of its SIMD: the loader's offsets
@@ -23,18 +24,12 @@
 #include <cmath>
 
 #include "common.h"
+#include "traj_stage.h"
 
 // (u - l)^2 and the sums are separate IEEE operations, as NumPy's are: exact data then gives NumPy's bits
 #pragma clang fp contract(off)
 
 namespace {
-
-constexpr int TE_THREADS = 256;
-constexpr int TE_RS = 32;                                 // rows of B per stage (two 16-row blocks)
-constexpr int TE_TB = 64;                                 // steps per workgroup (four 16-step tiles)
-constexpr int TE_TW = 2;                                  // step tiles per wave: wave w = row block w & 1, tiles 2 (w >> 1) ..
-constexpr int TE_NL = TE_RS * (128 / 2) / TE_THREADS;     // d2 loads of a B stage per thread at k = 128
-constexpr long TE_SLICE_ROWS = 1024;                      // shortest row slice
 
 struct TeParams {
   const double *B, *A, *U;
@@ -66,62 +61,9 @@ __global__ __launch_bounds__(TE_THREADS, 2) void traj_error_kernel(const TeParam
   const double* U = p.U ? p.U + traj * p.stride_u : nullptr;
   const bool want_ref = p.pref != nullptr;
 
-  {  // the coefficient block, once: rows t0 .. t0 + 63 of A, columns k .. kp - 1 and steps past nt zero
-    const bool avec = ((p.lda & 1) == 0) && ((reinterpret_cast<size_t>(A) & 15) == 0);
-    for (int q = tid; q < TE_TB * hp; q += TE_THREADS) {
-      const int r = q / hp, c = 2 * (q - r * hp);
-      d2 v{0.0, 0.0};
-      if (t0 + r < p.nt) {
-        const double* src = A + (t0 + r) * p.lda + c;
-        if (avec && c + 1 < p.k) {
-          v = *reinterpret_cast<const d2*>(src);
-        } else {
-          if (c < p.k) v.x = src[0];
-          if (c + 1 < p.k) v.y = src[1];
-        }
-      }
-      *reinterpret_cast<d2*>(&sC[r * S + c]) = v;
-    }
-  }
-
-  // B stage loader: what each thread loads, and where it goes, is the same for every stage
-  const bool bvec = ((p.ldb & 1) == 0) && ((reinterpret_cast<size_t>(p.B) & 15) == 0);
-  long goff[TE_NL];
-  int loff[TE_NL], code[TE_NL];                           // code: 0 nothing, 1 first word only, 2 two words, 3 one d2, 4 zeros; | row << 3
-  d2 breg[TE_NL];
-#pragma unroll
-  for (int i = 0; i < TE_NL; ++i) {
-    const int q = tid + TE_THREADS * i, r = q / hp, c = 2 * (q - r * hp);
-    int m = 0;
-    if (q < TE_RS * hp) m = c + 1 < p.k ? (bvec ? 3 : 2) : (c < p.k ? 1 : 4);
-    code[i] = m | (r << 3);
-    goff[i] = (long)r * p.ldb + c;
-    loff[i] = r * S + c;
-    breg[i] = d2{0.0, 0.0};
-  }
-  auto fetch = [&](long r0) {
-    const double* base = p.B + r0 * p.ldb;
-#pragma unroll
-    for (int i = 0; i < TE_NL; ++i) {
-      const int m = code[i] & 7;
-      d2 v{0.0, 0.0};
-      if (m >= 1 && m <= 3 && r0 + (code[i] >> 3) < p.N) {
-        const double* src = base + goff[i];
-        if (m == 3) {
-          v = *reinterpret_cast<const d2*>(src);
-        } else {
-          v.x = src[0];
-          if (m == 2) v.y = src[1];
-        }
-      }
-      breg[i] = v;
-    }
-  };
-  auto commit = [&]() {
-#pragma unroll
-    for (int i = 0; i < TE_NL; ++i)
-      if (code[i] & 7) *reinterpret_cast<d2*>(&sB[loff[i]]) = breg[i];
-  };
+  te_load_coefficients(sC, A, p.lda, t0, p.nt, p.k, hp, S, tid);
+  TeStageLoader stage;
+  stage.init(p.B, p.ldb, p.N, p.k, hp, S, sB, tid);
 
   // this lane's words of the U tile, in the accumulator layout (tile j, register c): row (lane >> 4) + 4 c, column lane & 15
   long uoff[TE_TW][4];
@@ -144,14 +86,14 @@ __global__ __launch_bounds__(TE_THREADS, 2) void traj_error_kernel(const TeParam
 #pragma unroll
     for (int c = 0; c < 4; ++c) se[j][c] = sr[j][c] = 0.0;
 
-  fetch(row_lo);
-  commit();
+  stage.fetch(row_lo);
+  stage.commit();
   __syncthreads();
   const double* fb = sB + (16 * rb + l15) * S + l4;       // operand words: index lane & 15, k = 4 k4 + (lane >> 4)
   const double* fc = sC + (16 * TE_TW * tg + l15) * S + l4;
   for (long r0 = row_lo; r0 < row_hi; r0 += TE_RS) {
     const bool more = r0 + TE_RS < row_hi;
-    if (more) fetch(r0 + TE_RS);
+    if (more) stage.fetch(r0 + TE_RS);
     double u[TE_TW][4];
     if (U) {
       const double* ub = U + (COLMAJ ? r0 : r0 * p.ldu);
@@ -191,7 +133,7 @@ __global__ __launch_bounds__(TE_THREADS, 2) void traj_error_kernel(const TeParam
         se[j][c] += d * d;
       }
     __syncthreads();
-    if (more) commit();
+    if (more) stage.commit();
     __syncthreads();
   }
 

@@ -208,6 +208,46 @@ def trajectory_errors(B: torch.Tensor, A: torch.Tensor, U: torch.Tensor = None, 
     return (err, ref) if want_ref else err
 
 
+FN_KINDS = dict(power=0)       # RT_FN_*
+
+
+def trajectory_integrals(E: torch.Tensor, A: torch.Tensor, w: torch.Tensor = None, scale: torch.Tensor = None,
+                         fn=("power", 0.0, 1.0, 1.0)) -> torch.Tensor:
+    """out[j, t] = scale[j, t] * sum_i w[i] f(E[i, :] . A_j[t, :]) without storing the lifted trajectories E A_j^T
+    (rt_trajectory_integrals).  E: n_pts x k basis at the quadrature points (k <= 128); A: (nt, k) or (n, nt, k)
+    coefficients, as the sweeps return them; w: n_pts weights or None (1); scale: (n, nt) (or (nt,) for one trajectory) or
+    None (1); fn: ("power", c0, c1, p) for f(z) = (c0 + c1 z)^p.  Returns (n, nt)."""
+    ctx = Context.current()
+    for name, t in (("E", E), ("A", A), ("w", w), ("scale", scale)):
+        if t is not None and (t.dtype != torch.float64 or not t.is_cuda):
+            raise RomtimeHipError(f"trajectory_integrals: {name} must be a float64 CUDA tensor")
+    if E.dim() != 2 or A.dim() not in (2, 3):
+        raise RomtimeHipError("trajectory_integrals: E must be 2-D, A 2-D or 3-D")
+    if len(fn) != 4 or fn[0] not in FN_KINDS:
+        raise RomtimeHipError(f"trajectory_integrals: fn must be ('power', c0, c1, p), not {fn!r}")
+    if A.dim() == 2:
+        A = A.unsqueeze(0)
+    n_pts, k = E.shape
+    n, nt, k2 = A.shape
+    if scale is not None and scale.dim() == 1 and n == 1:
+        scale = scale.unsqueeze(0)
+    if k2 != k or (w is not None and tuple(w.shape) != (n_pts,)) or (scale is not None and tuple(scale.shape) != (n, nt)):
+        raise RomtimeHipError(f"trajectory_integrals: shapes do not match (E {tuple(E.shape)}, A {tuple(A.shape)}, "
+                              f"w {None if w is None else tuple(w.shape)}, scale {None if scale is None else tuple(scale.shape)})")
+    if _layout_last2(E) is None or _layout_last2(E)[1] != ROW_MAJOR:
+        E = E.contiguous()
+    if _layout_last2(A) is None or _layout_last2(A)[1] != ROW_MAJOR:
+        A = A.contiguous()
+    lde, lda = _layout_last2(E)[0], _layout_last2(A)[0]
+    w = None if w is None else w.contiguous()
+    scale = None if scale is None else scale.contiguous()
+    par = (C.c_double * 3)(float(fn[1]), float(fn[2]), float(fn[3]))
+    out = torch.empty((n, nt), dtype=torch.float64, device=E.device)
+    ctx.check(ctx.lib.rt_trajectory_integrals(ctx.handle, _ptr(E), lde, _ptr(w), _ptr(A), lda, A.stride(0), _ptr(scale), n_pts, k,
+                                              nt, n, FN_KINDS[fn[0]], par, _ptr(out)), "rt_trajectory_integrals")
+    return out
+
+
 def rank_update(Ysrc: torch.Tensor, X: torch.Tensor, T: torch.Tensor, alpha: float = -1.0, colscale: torch.Tensor = None,
                 out: torch.Tensor = None) -> torch.Tensor:
     """``out = Ysrc diag(colscale) + alpha X T`` for a tall row-major Ysrc (N x n), thin X (N x k) and T (k x n);
