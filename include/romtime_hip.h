@@ -344,6 +344,34 @@ int rt_trajectory_integrals_plan_info(int num_cus, const double* E, int64_t lde,
                                       int64_t stride_a, const double* scale, int64_t n_pts, int64_t k, int64_t nt,
                                       int64_t n_traj, int fn, const double* par, const double* out, int64_t* info3);
 
+/* ---- certification of the (M)DEIM interpolants over whole snapshot sets (evaluate of the three classes, deim.py:226-261
+ *      and nonlinear.py:470-540; run by default for every hyper-reductor, hrom.py:491-502, 796-809) ---- */
+/* err[q] = (1/group) sum_{i < group} || f_s - I(f_s) ||_2 / sqrt(N), s = q group + i, for the S snapshots of F, since
+ * version 380; I(f) = Psi f[idx] with entry pin_row replaced by pin_value where pin_row >= 0 (MDEIM's Dirichlet entry,
+ * deim.py:449-450), and ref[q] (may be NULL) the same mean of || f_s ||_2 / sqrt(N), always of the data as they are.  No
+ * theta array, interpolant or modified copy of the snapshots is stored.  Psi: N x m row-major DEVICE matrix (ldpsi >= m),
+ * the basis with the theta solve folded in, basis_fom PT_U^-1; m <= 128 (RT_ERR_UNSUPPORTED beyond).  idx: m HOST flat
+ * indices into a snapshot, each checked to lie in [0, N) before anything is launched (RT_ERR_ARG otherwise): the
+ * coefficients of a snapshot are its own entries at idx.  F: N x S DEVICE matrix (ldf, f_layout); RT_COL_MAJOR = every
+ * snapshot contiguous (what rt_p1_local_assembly writes).  err, ref: S / group DEVICE values.  Any legal leading
+ * dimensions, 8-byte aligned bases.  Null Psi, idx, F or err, sizes < 1, S % group != 0, pin_row outside [-1, N), an
+ * unknown layout and short leading dimensions return RT_ERR_ARG, all before any launch.
+ *   - (f - l), the square and the sums are separate IEEE operations, sqrt and the divisions correctly rounded; the group
+ *     mean is a running sum in index order and one division, as nonlinear.py:518-535 forms it.
+ *   - No floating-point atomics: partial sums are written as [snapshot][row slice] (ctx leaf arena) and a finish kernel
+ *     adds the slices in order.  The slicing depends on N and the ctx's CU count only, so the bits of a snapshot's error
+ *     depend neither on S, its place in the block, nor group: a set may be handed over in chunks.
+ *   - rt_last_launch_info: [0] workgroups, [1] row slices, [2] tile 32 rows x 64 snapshots. */
+int rt_interpolation_errors(rt_ctx* ctx, const double* Psi, int64_t ldpsi, const int64_t* idx, int64_t m, const double* F,
+                            int64_t ldf, int f_layout, int64_t N, int64_t S, int64_t group, int64_t pin_row, double pin_value,
+                            double* err, double* ref);
+/* The argument checks and the launch plan of rt_interpolation_errors for a ctx of num_cus CUs - host logic only, no GPU:
+ * idx (a host array) is read, no other pointer is followed.  The same return code, and on RT_OK info3 (may be NULL) as
+ * rt_last_launch_info reports it. */
+int rt_interpolation_errors_plan_info(int num_cus, const double* Psi, int64_t ldpsi, const int64_t* idx, int64_t m,
+                                      const double* F, int64_t ldf, int f_layout, int64_t N, int64_t S, int64_t group,
+                                      int64_t pin_row, double pin_value, const double* err, const double* ref, int64_t* info3);
+
 /* ---- closed-form local assembly of the 1-D P1 operators at (M)DEIM entries (the step before the path) ----------
  * What ``assemble(mu, t, entries=dofs[, u_n])`` returns for the reference's 1-D problems (fom/base.py:523-599 per-entry
  * assembly of the forms in fom/nonlinear.py:374-494; closed forms as in testing/mock.py:30-85), for n_states states at

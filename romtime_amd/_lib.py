@@ -75,6 +75,9 @@ SIGNATURES = {
     "rt_trajectory_integrals": (_int, [_p, _p, _i64, _p, _p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _int, C.POINTER(C.c_double), _p]),
     "rt_trajectory_integrals_plan_info": (_int, [_int, _p, _i64, _p, _p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _int,
                                                  C.POINTER(C.c_double), _p, C.POINTER(_i64)]),
+    "rt_interpolation_errors": (_int, [_p, _p, _i64, C.POINTER(_i64), _i64, _p, _i64, _int, _i64, _i64, _i64, _i64, C.c_double, _p, _p]),
+    "rt_interpolation_errors_plan_info": (_int, [_int, _p, _i64, C.POINTER(_i64), _i64, _p, _i64, _int, _i64, _i64, _i64, _i64,
+                                                 C.c_double, _p, _p, C.POINTER(_i64)]),
     "rt_p1_local_assembly": (_int, [_p, _int, _i64, _p, _p, _i64, _i64, _p, _p, _int, _p, _p]),
     "rt_sym_eig_values": (_int, [_p, _p, _i64, _p, _p]),
     "rt_sym_eig_values_part": (_int, [_p, _p, _i64, _i64, _i64, _p, _p]),

@@ -1,6 +1,7 @@
-// What the kernels that walk a tall basis against a block of trajectory steps share (traj_error.hip, traj_output.hip):
-// the tile sizes, the load of the 64 x k coefficient block into LDS, and the loader that takes 32 x k stages of the
-// basis global -> registers -> LDS with the next stage in flight while the current one is multiplied.
+// What the kernels that walk a tall basis against a block of trajectory steps share (traj_error.hip, traj_output.hip,
+// interp_error.hip): the tile sizes, the load (or gather) of the 64 x k coefficient block into LDS, and the loader that
+// takes 32 x k stages of the basis global -> registers -> LDS with the next stage in flight while the current one is
+// multiplied.
 #pragma once
 #include "common.h"
 
@@ -31,6 +32,20 @@ __device__ __forceinline__ void te_load_coefficients(double* sC, const double* A
       }
     }
     *reinterpret_cast<d2*>(&sC[r * S + c]) = v;
+  }
+}
+
+// the coefficient block gathered from the data itself (interp_error.hip): word (r, c) is row idx[c] of snapshot t0 + r of
+// the N x nt matrix F; columns k .. kp - 1 and snapshots past nt zero.  With every snapshot contiguous (COLMAJ) the
+// threads run along c, otherwise along r, where the words of one row of F lie side by side.
+template <bool COLMAJ>
+__device__ __forceinline__ void te_gather_coefficients(double* sC, const double* F, long ldf, const long* idx, long t0, long nt,
+                                                       int k, int kp, int S, int tid) {
+  for (int q = tid; q < TE_TB * kp; q += TE_THREADS) {
+    const int r = COLMAJ ? q / kp : q % TE_TB, c = COLMAJ ? q - r * kp : q / TE_TB;
+    double v = 0.0;
+    if (c < k && t0 + r < nt) v = COLMAJ ? F[(t0 + r) * ldf + idx[c]] : F[idx[c] * ldf + t0 + r];
+    sC[r * S + c] = v;
   }
 }
 

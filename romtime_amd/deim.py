@@ -60,6 +60,10 @@ class InterpolationSelector:
 
 class DiscreteEmpiricalInterpolation(Reductor):
     TYPE = EmpiricalInterpolation.DEIM
+    # Where ``evaluate`` runs.  "host": the reference's loop, one sample at a time (two FOM callbacks, a theta solve and an
+    # expansion each).  "device": ``interpolation.evaluate`` - the snapshots of a parameter point certified by one kernel
+    # call (rt_interpolation_errors); its errors differ from the host loop's by rounding, so the caller chooses.
+    EVALUATE_ON = "host"
 
     def __init__(self, assemble, grid=None, tree_walk_params=None, name=None) -> None:
         super().__init__(grid=grid)
@@ -105,7 +109,14 @@ class DiscreteEmpiricalInterpolation(Reductor):
             value = getattr(self, attr)
             if value is not None:
                 setattr(new, attr, deepcopy(value))
+        if "EVALUATE_ON" in self.__dict__:
+            new.EVALUATE_ON = self.EVALUATE_ON
         return new
+
+    def _evaluate_on_device(self):
+        if self.EVALUATE_ON not in ("host", "device"):
+            raise ValueError(f"EVALUATE_ON must be 'host' or 'device', not {self.EVALUATE_ON!r}")
+        return self.EVALUATE_ON == "device"
 
     # ---- device residency of the (large) bases -----------------------------------------
     def _device(self, key, array):
@@ -270,6 +281,10 @@ class DiscreteEmpiricalInterpolation(Reductor):
 
     def evaluate(self, ts, num=None, mu_space=None):
         """Accuracy harness: interpolation error on fresh parameters (deim.py:226-261)."""
+        if self._evaluate_on_device():
+            from . import interpolation
+
+            return interpolation.evaluate(self, ts, num=num, mu_space=mu_space)
         if mu_space:
             space = mu_space
         else:

@@ -137,6 +137,10 @@ class MatrixDiscreteEmpiricalInterpolationNonlinear(MatrixDiscreteEmpiricalInter
 
     def evaluate(self, ts, funcs=None, num=None, mu_space=None):
         """Mean interpolation error over the state basis (nonlinear.py:470-540)."""
+        if self._evaluate_on_device():
+            from . import interpolation
+
+            return interpolation.evaluate(self, ts, num=num, mu_space=mu_space, funcs=funcs)
         if mu_space:
             space = mu_space
         else:

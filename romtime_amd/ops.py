@@ -248,6 +248,40 @@ def trajectory_integrals(E: torch.Tensor, A: torch.Tensor, w: torch.Tensor = Non
     return out
 
 
+def interpolation_errors(Psi: torch.Tensor, idx, F: torch.Tensor, group: int = 1, pin=None, want_ref: bool = False):
+    """err[q] = mean over the ``group`` snapshots s = q group + i of ||F[:, s] - I(F[:, s])||_2 / sqrt(N), with
+    I(f) = Psi f[idx] (rt_interpolation_errors): the (M)DEIM interpolation error of every snapshot of a block, neither
+    thetas nor interpolants stored.  Psi: N x m (m <= 128), the basis with the theta solve folded in
+    (``interpolation.fold``); idx: m flat indices on the host, each in [0, N); F: N x S snapshots, either memory order;
+    pin: None or (row, value), the entry of the interpolant that is replaced by a constant (MDEIM's Dirichlet entry).
+    Returns err (S / group,), and with ``want_ref`` also the same mean of ||F[:, s]||_2 / sqrt(N)."""
+    ctx = Context.current()
+    for name, t in (("Psi", Psi), ("F", F)):
+        if t.dtype != torch.float64 or not t.is_cuda or t.dim() != 2:
+            raise RomtimeHipError(f"interpolation_errors: {name} must be a 2-D float64 CUDA tensor")
+    N, m = Psi.shape
+    S = F.shape[1]
+    idx = np.ascontiguousarray(np.asarray(idx, dtype=np.int64).reshape(-1))
+    group = int(group)
+    if F.shape[0] != N or idx.size != m or group < 1 or S % group:
+        raise RomtimeHipError(f"interpolation_errors: shapes do not match (Psi {tuple(Psi.shape)}, idx {idx.size}, "
+                              f"F {tuple(F.shape)}, group {group})")
+    if _layout_last2(Psi) is None or _layout_last2(Psi)[1] != ROW_MAJOR:
+        Psi = Psi.contiguous()
+    if _layout_last2(F) is None:
+        F = F.contiguous()
+    ldpsi, (ldf, lf) = _layout_last2(Psi)[0], _layout_last2(F)
+    pin_row, pin_value = (-1, 0.0) if pin is None else (int(pin[0]), float(pin[1]))
+    if pin is not None and not 0 <= pin_row < N:
+        raise RomtimeHipError(f"interpolation_errors: pinned row {pin_row} outside [0, {N})")
+    err = torch.empty(S // group, dtype=torch.float64, device=Psi.device)
+    ref = torch.empty(S // group, dtype=torch.float64, device=Psi.device) if want_ref else None
+    ctx.check(ctx.lib.rt_interpolation_errors(ctx.handle, _ptr(Psi), ldpsi, idx.ctypes.data_as(C.POINTER(C.c_int64)), m, _ptr(F),
+                                              ldf, lf, N, S, group, pin_row, pin_value, _ptr(err), _ptr(ref)),
+              "rt_interpolation_errors")
+    return (err, ref) if want_ref else err
+
+
 def rank_update(Ysrc: torch.Tensor, X: torch.Tensor, T: torch.Tensor, alpha: float = -1.0, colscale: torch.Tensor = None,
                 out: torch.Tensor = None) -> torch.Tensor:
     """``out = Ysrc diag(colscale) + alpha X T`` for a tall row-major Ysrc (N x n), thin X (N x k) and T (k x n);
