@@ -397,6 +397,47 @@ int rt_p1_local_assembly(rt_ctx* ctx, int kind, int64_t nx, const int64_t* rows,
                          int64_t n_states, const double* h, const double* coef, int state_mode, const double* state,
                          double* out);
 
+/* ---- full-order BDF sweeps of the closed-form 1-D P1 models (the time loop of OneDimensionalSolver.solve,
+ *      fom/base.py:693-831, for the heat problem fom/heat.py:57-82, 251-262 and the piston fom/nonlinear.py:322-494;
+ *      testing/mock.py: MockHeatEquation.solve, MockBurgers.solve) for a batch of parameter points, since version 390 ---- */
+typedef struct {
+  int64_t nx, n_mu, nt;    /* cells (N_h = nx + 1 >= 3), parameter points, steps of THIS call */
+  int64_t first_step;      /* global index of this call's first step: the step with global index 0 is BDF1 */
+  double dt;
+  int bdf2;                /* as rt_sweep_desc */
+  int state_in_w;          /* 1: w includes u* (Burgers), 0: linear problem (heat) */
+  const double* tab;       /* nt x n_mu x 7 DEVICE: h, alpha, c0, c1, a0, a1, a2 of step s, point j */
+  const double* u_init;    /* NULL = zero state (then first_step must be 0), else n_mu x 2 x N_h DEVICE: u^n, u^{n-1} */
+} rt_fom_desc;             /* host struct */
+/* Every step solves, for each point, the tridiagonal system of the interior rows i = 1 .. nx-1
+ *     l_i = bdf h/6 + dt(-alpha/h - b_{i-1}),  d_i = bdf 4h/6 + dt(2 alpha/h + b_{i-1} - a_i),  u_i = bdf h/6 + dt(-alpha/h + a_i),
+ *     rhs_i = h/6 (past_{i-1} + 4 past_i + past_{i+1}) + dt h/3 (f(x_i - h/2) + f(x_i) + f(x_i + h/2)),  x_i = i h,
+ * with a_e = (2 w_e + w_{e+1})/6, b_e = (w_e + 2 w_{e+1})/6 per cell of the nodal function w_i = s u*_i + c0 + c1 i/nx
+ * (s = state_in_w), f = a0 + a1 x + a2 x^2 (the RT_P1_LOAD_P2 rule), and bdf = 1.5, u* = 2u^n - u^{n-1}, past = 2u^n -
+ * u^{n-1}/2 from global step 1 on when bdf2 is set, otherwise 1, u^n, u^n: mass + stiffness + ONE trilinear form, which
+ * covers MockSolver's constant convection (c0 = -1), the ALE ramp of the moving heat problem and the lifting ramp of the
+ * piston (c1), and the state.  The Dirichlet values u_0 = u_nx = 0 are written as zeros.
+ *   - U_out: trajectory j starts at U_out + j stride_mu and its step s is the N_h contiguous values at + s ld_step - the
+ *     RT_COL_MAJOR N_h x nt snapshot matrix that rt_gram, rt_pod_orth and rt_trajectory_errors take unchanged.
+ *   - info: n_mu DEVICE ints, each 0, or 1 + the global index of the first step in which some row is not diagonally
+ *     dominant (|d| < |l| + |u|) or a pivot is not finite.  The sweep of a flagged point carries on (there is no pivoting,
+ *     so its values are then not to be trusted); a flag never affects another point.
+ *   - Null desc, tab, U_out or info, sizes < 1, nx < 2, ld_step < N_h, trajectories that overlap (n_mu > 1 needs
+ *     stride_mu >= (nt-1) ld_step + N_h) and u_init == NULL with first_step != 0 return RT_ERR_ARG before any launch.  nx <= 2^22; beyond, or where the states and factors
+ *     of the call (40 KiB x ceil((nx-1)/1024) per point, ctx leaf arena) exceed 64 GiB, RT_ERR_UNSUPPORTED.
+ *   - One workgroup per parameter point and the whole time loop in one launch; no workgroup waits for another, so n_mu may
+ *     exceed the CU count, nothing can time out and a CU-masked stream gives the same bits.  Each of up to 1024 threads
+ *     eliminates a partition of consecutive rows formed on the fly, the partitions' last unknowns are solved for in LDS
+ *     by cyclic reduction, and the back-substitution inside every partition follows; no pivoting, no floating-point atomics.
+ *   - The bits of a trajectory depend on nx, its own table rows, dt and the flags only - not on n_mu, the point's place in
+ *     the batch, the ctx's CU count or how the horizon is cut into calls (u_init = the two last states of the call before).
+ *   - rt_last_launch_info: [0] workgroups, [1] partitions per system, [2] rows per partition. */
+int rt_p1_fom_bdf_sweep(rt_ctx* ctx, const rt_fom_desc* desc, double* U_out, int64_t ld_step, int64_t stride_mu, int* info);
+/* The argument checks and the partitioning of rt_p1_fom_bdf_sweep - host logic only, no GPU and no pointer but desc is
+ * followed (U_out and info, which it does not take, count as given): the same return code, and on RT_OK info3 (may be
+ * NULL) = {workgroups, partitions per system, rows per partition}. */
+int rt_p1_fom_bdf_sweep_plan_info(int num_cus, const rt_fom_desc* desc, int64_t ld_step, int64_t stride_mu, int64_t* info3);
+
 /* ---- small symmetric eigenproblem of the Gram matrix, on the device (3 <= n <= 2048) ---------- */
 /* Householder tridiagonalisation (32 cooperating workgroups, 128 for n > 512; matrix resident in LDS) + Sturm
  * multisection:

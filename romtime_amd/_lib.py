@@ -79,6 +79,8 @@ SIGNATURES = {
     "rt_interpolation_errors_plan_info": (_int, [_int, _p, _i64, C.POINTER(_i64), _i64, _p, _i64, _int, _i64, _i64, _i64, _i64,
                                                  C.c_double, _p, _p, C.POINTER(_i64)]),
     "rt_p1_local_assembly": (_int, [_p, _int, _i64, _p, _p, _i64, _i64, _p, _p, _int, _p, _p]),
+    "rt_p1_fom_bdf_sweep": (_int, [_p, _p, _p, _i64, _i64, _p]),
+    "rt_p1_fom_bdf_sweep_plan_info": (_int, [_int, _p, _i64, _i64, C.POINTER(_i64)]),
     "rt_sym_eig_values": (_int, [_p, _p, _i64, _p, _p]),
     "rt_sym_eig_values_part": (_int, [_p, _p, _i64, _i64, _i64, _p, _p]),
     "rt_sym_eig_vectors": (_int, [_p, _i64, _i64, _p, _p]),
@@ -105,6 +107,13 @@ class HSweepDesc(C.Structure):
     _fields_ = [("r", _i64), ("n_mu", _i64), ("nt", _i64), ("dt", C.c_double), ("bdf2", _int), ("m_mass", _i64),
                 ("m_lin", _i64), ("m_nl", _i64), ("m_rhs", _i64), ("Z", _p), ("Zf", _p), ("F_mass", _p), ("F_lin", _p),
                 ("F_rhs", _p), ("W", _p), ("C_nl", _p), ("S_nl", _p)]
+
+
+class FomDesc(C.Structure):
+    """rt_fom_desc of include/romtime_hip.h."""
+
+    _fields_ = [("nx", _i64), ("n_mu", _i64), ("nt", _i64), ("first_step", _i64), ("dt", C.c_double), ("bdf2", _int),
+                ("state_in_w", _int), ("tab", _p), ("u_init", _p)]
 
 
 _lib = None

@@ -1,0 +1,364 @@
+// Full-order BDF sweeps of the closed-form 1-D P1 models (testing/mock.py: MockHeatEquation.solve, MockBurgers.solve;
+// the reference's OneDimensionalSolver.solve, fom/base.py:693-831) for a batch of parameter points, the whole time loop in
+// one launch.
+//
+// Every operator of the two problems has a closed form per row (p1_assembly.hip), and every convective operator is the
+// trilinear form int w u' v of a nodal function  w_i = s u*_i + c0 + c1 i/nx  (s = 1: Burgers, the state convects; c0 = -1
+// MockSolver's constant convection; c1 the ALE ramp of the moving heat problem or the lifting ramp of the piston).  A step is
+// therefore ONE tridiagonal system per parameter point, interior rows i = 1 .. nx-1:
+//
+//   a_e = (2 w_e + w_e+1)/6,  b_e = (w_e + 2 w_e+1)/6                                   per cell e
+//   l_i = bdf h/6 + dt(-alpha/h - b_i-1)
+//   d_i = bdf 4h/6 + dt(2 alpha/h + b_i-1 - a_i)
+//   u_i = bdf h/6 + dt(-alpha/h + a_i)
+//   rhs_i = h/6 (past_i-1 + 4 past_i + past_i+1) + dt h/3 (f(x_i - h/2) + f(x_i) + f(x_i + h/2)),  f = a0 + a1 x + a2 x^2
+//
+// with bdf = 1.5, u* = 2u^n - u^n-1, past = 2u^n - u^n-1/2 from global step 1 on under BDF2, else 1, u^n, u^n.
+//
+// One workgroup of 1024 threads per parameter point; no workgroup ever waits for another, so there is no co-residency
+// requirement, n_mu may exceed the CU count and a CU-masked stream gives the same bits.  The rows are never stored: each
+// thread owns a partition of m = ceil((nx-1)/1024) consecutive rows and forms them on the fly (Wang's partition method,
+// no pivoting - the rows are diagonally dominant, which info reports):
+//
+//   A  downward elimination inside the partition:   x_k + c_k x_k+1 + f_k xL = y_k      (xL: last unknown of partition p-1)
+//      and, in the same pass, the partition's first unknown  x_0 = Y - G xB - F xL       (xB: its own last unknown)
+//      as running sums with the products pi_k+1 = -c_k pi_k
+//   B  the partitions' last unknowns satisfy a tridiagonal system of <= 1024 rows:
+//        f_last xB_p-1 + (1 - c_last F_p+1) xB_p - c_last G_p+1 xB_p+1 = y_last - c_last Y_p+1
+//      solved in LDS by parallel cyclic reduction, log2 steps, every thread one row
+//   C  upwards, x_k = y_k - c_k x_k+1 - f_k xL from x_last = xB, written to the new state and, through an LDS tile, to U_out
+//
+// A step moves ten arrays of N_h words through its CU (two states in, three factors out and in again, the new state and
+// U_out), and a workgroup has the vector memory path of one CU for it.
+//
+// The two states and the three factor arrays of a point live in the ctx's leaf arena as [row of partition][partition]:
+// lane p reads and writes element p of a row, so every access of A and C is coalesced, and the neighbours across a
+// partition edge are lane p-1's last and lane p+1's first row.  Only U_out and u_init have the natural layout: they pass
+// through an LDS tile of 8 rows of every partition (64-byte runs in memory).
+#include <cmath>
+
+#include "common.h"
+
+namespace {
+
+constexpr int FOM_THREADS = 1024;            // partitions of a system at most: one per thread
+constexpr int FOM_KT = 8;                    // rows of every partition in one LDS tile
+constexpr int FOM_TILE_LD = FOM_KT + 1;
+constexpr int FOM_KB = 8;                    // rows of pass A whose loads are issued together
+constexpr long FOM_MAX_NX = 1L << 22;        // stated in the header
+constexpr size_t FOM_MAX_SCRATCH = (size_t)1 << 36;
+constexpr int FOM_LDS_BYTES = (FOM_THREADS * FOM_TILE_LD + FOM_THREADS) * 8;   // tile (the PCR rows alias it) + xB
+
+struct FomParams {
+  long nx, n_mu, nt, first_step, m, parts, ld_step, stride_mu;
+  double dt;
+  int bdf2, state_in_w;
+  const double* tab;
+  const double* u_init;
+  double* U;
+  int* info;
+  double* arena;
+};
+
+struct FomPlan {
+  long m, parts;
+  size_t scratch;
+};
+
+// rows k0 .. k0+KT-1 of every partition between the LDS tile and a state in its natural layout (node = 1 + p m + k)
+__device__ __forceinline__ void fom_tile_to_global(const double* tile, double* dst, int k0, int m, int n) {
+  for (int it = 0; it < FOM_KT; ++it) {
+    const int idx = threadIdx.x + it * FOM_THREADS;
+    const int q = idx / FOM_KT, kk = idx % FOM_KT;
+    const int k = k0 + kk, row = q * m + k;
+    if (k < m && row < n) dst[1 + row] = tile[q * FOM_TILE_LD + kk];
+  }
+}
+
+__device__ __forceinline__ void fom_global_to_tile(double* tile, const double* src, int k0, int m, int n) {
+  for (int it = 0; it < FOM_KT; ++it) {
+    const int idx = threadIdx.x + it * FOM_THREADS;
+    const int q = idx / FOM_KT, kk = idx % FOM_KT;
+    const int k = k0 + kk, row = q * m + k;
+    if (k < m && row < n) tile[q * FOM_TILE_LD + kk] = src[1 + row];
+  }
+}
+
+// nx <= 2^22: node numbers and the offsets inside a point's arrays (m x 1024 <= 2^22 words) fit 32 bits
+__global__ __launch_bounds__(FOM_THREADS) void p1_fom_kernel(const FomParams P) {
+  extern __shared__ double fom_lds[];
+  double* tile = fom_lds;                               // FOM_THREADS x FOM_TILE_LD
+  double* pcr = fom_lds;                                // 4 x FOM_THREADS, while no tile is in flight
+  double* shb = fom_lds + FOM_THREADS * FOM_TILE_LD;    // FOM_THREADS: xB of every partition
+  constexpr int NT = FOM_THREADS;
+  const int p = threadIdx.x;
+  const long j = blockIdx.x;
+  const int m = (int)P.m, n = (int)P.nx - 1;
+  const int r0 = p * m;
+  const int mp = n - r0 > m ? m : (n - r0 < 0 ? 0 : n - r0);   // rows of this partition (only the last active one may be short)
+  const bool active = mp > 0;
+  const bool last_part = active && (r0 + mp == n);
+  double* base = P.arena + (size_t)j * 5 * m * NT;
+  double* S0 = base;                                    // u^n
+  double* S1 = base + (size_t)m * NT;                   // u^{n-1}; the new state is written over it
+  double* const fc = base + (size_t)2 * m * NT;
+  double* const ff = base + (size_t)3 * m * NT;
+  double* const fy = base + (size_t)4 * m * NT;
+
+  if (P.u_init) {
+    for (int which = 0; which < 2; ++which) {
+      const double* src = P.u_init + ((size_t)j * 2 + which) * (P.nx + 1);
+      double* S = which ? S1 : S0;
+      for (int k0 = 0; k0 < m; k0 += FOM_KT) {
+        fom_global_to_tile(tile, src, k0, m, n);
+        __syncthreads();
+        for (int kk = 0; kk < FOM_KT; ++kk)
+          if (k0 + kk < mp) S[(k0 + kk) * NT + p] = tile[p * FOM_TILE_LD + kk];
+        __syncthreads();
+      }
+    }
+  } else {
+    for (int k = 0; k < mp; ++k) S0[k * NT + p] = S1[k * NT + p] = 0.0;
+    __syncthreads();
+  }
+
+  const double dt = P.dt, inv_nx = 1.0 / (double)P.nx, sixth = 1.0 / 6.0;
+  const double ws = P.state_in_w ? 1.0 : 0.0;
+  int info = 0;
+  for (long s = 0; s < P.nt; ++s) {
+    const long g = P.first_step + s;
+    const bool two = P.bdf2 && g > 0;
+    const double* tb = P.tab + ((size_t)s * P.n_mu + j) * 7;
+    const double h = tb[0], alpha = tb[1], c0 = tb[2], c1 = tb[3], a0 = tb[4], a1 = tb[5], a2 = tb[6];
+    const double bdf = two ? 1.5 : 1.0;
+    const double mo = bdf * h / 6.0, md = bdf * 4.0 * h / 6.0, ah = alpha / h, h6 = h / 6.0, dth = dt * h;
+    const double c1n = c1 * inv_nx, a2h = a2 * h * h / 6.0;
+    bool bad = false;
+    double cl = 0.0, fl = 0.0, yl = 0.0;   // the partition's last row after A
+    double Y = 0.0, G = 0.0, F = 0.0;      // its first unknown in terms of xB and xL
+
+    if (active) {
+      // ---- A: rows formed from a sliding window of three nodes and eliminated downwards.  The first unknown follows
+      // from the same pass: x_0 = sum_k pi_k (y_k - f_k xL) + pi_last xB with pi_0 = 1, pi_k+1 = -c_k pi_k.
+      double unL = 0.0, vnL = 0.0;
+      if (p > 0) {
+        unL = S0[(m - 1) * NT + p - 1];
+        if (two) vnL = S1[(m - 1) * NT + p - 1];
+      }
+      const double unC = S0[p], vnC = two ? S1[p] : 0.0;
+      double wL = ws * (two ? 2.0 * unL - vnL : unL) + c0 + c1n * (double)r0;
+      double wC = ws * (two ? 2.0 * unC - vnC : unC) + c0 + c1n * (double)(r0 + 1);
+      double pL = two ? 2.0 * unL - 0.5 * vnL : unL, pC = two ? 2.0 * unC - 0.5 * vnC : unC;
+      double cprev = 0.0, fprev = -1.0, yprev = 0.0, pi = 1.0;
+      for (int kb = 0; kb < mp; kb += FOM_KB) {
+        // the right-hand neighbours of FOM_KB rows are asked for together: the elimination below is one dependent chain,
+        // and a load per row inside it would put a trip to the L2 on that chain
+        double ur[FOM_KB], vr[FOM_KB];
+#pragma unroll
+        for (int q = 0; q < FOM_KB; ++q) {
+          const int k = kb + q;
+          ur[q] = vr[q] = 0.0;
+          if (k + 1 < mp) {
+            ur[q] = S0[(k + 1) * NT + p];
+            if (two) vr[q] = S1[(k + 1) * NT + p];
+          } else if (k + 1 == mp && !last_part) {
+            ur[q] = S0[p + 1];
+            if (two) vr[q] = S1[p + 1];
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < FOM_KB; ++q) {
+          const int k = kb + q;
+          if (k >= mp) break;
+          const int i = r0 + k + 1;         // node of this row
+          const double unR = ur[q], vnR = vr[q];
+          const double wR = ws * (two ? 2.0 * unR - vnR : unR) + c0 + c1n * (double)(i + 1);
+          const double pR = two ? 2.0 * unR - 0.5 * vnR : unR;
+          const double bp = (wL + 2.0 * wC) * sixth, ai = (2.0 * wC + wR) * sixth;
+          double l = mo + dt * (-ah - bp);
+          const double d = md + dt * (2.0 * ah + bp - ai);
+          double u = mo + dt * (-ah + ai);
+          // h/3 (f(x - h/2) + f(x) + f(x + h/2)) = h (f(x) + a2 h^2 / 6) for the quadratic f
+          const double x = (double)i * h;
+          const double rhs = h6 * (pL + 4.0 * pC + pR) + dth * (fma(fma(a2, x, a1), x, a0) + a2h);
+          bad |= fabs(d) < fabs(l) + fabs(u);
+          if (i == 1) l = 0.0;              // u_0 = u_nx = 0
+          if (i == n) u = 0.0;
+          const double r = 1.0 / (d - l * cprev);
+          bad |= !std::isfinite(r);
+          const double c = u * r, f = -l * fprev * r, y = (rhs - l * yprev) * r;
+          fc[k * NT + p] = c;
+          ff[k * NT + p] = f;
+          fy[k * NT + p] = y;
+          if (k + 1 < mp) {
+            Y += pi * y;
+            F += pi * f;
+            pi = -c * pi;
+          }
+          cprev = c, fprev = f, yprev = y;
+          wL = wC, wC = wR, pL = pC, pC = pR;
+        }
+      }
+      cl = cprev, fl = fprev, yl = yprev;
+      G = -pi;
+    }
+
+    // ---- B: the system of the partitions' last unknowns
+    pcr[p] = Y;
+    pcr[NT + p] = G;
+    pcr[2 * NT + p] = F;
+    __syncthreads();
+    const bool nb = p + 1 < FOM_THREADS;
+    const double Yn = nb ? pcr[p + 1] : 0.0, Gn = nb ? pcr[NT + p + 1] : 0.0, Fn = nb ? pcr[2 * NT + p + 1] : 0.0;
+    __syncthreads();
+    double A = active ? fl : 0.0, B = active ? 1.0 - cl * Fn : 1.0, C = active ? -cl * Gn : 0.0, D = active ? yl - cl * Yn : 0.0;
+    for (int st = 1; st < P.parts; st <<= 1) {
+      pcr[p] = A;
+      pcr[NT + p] = B;
+      pcr[2 * NT + p] = C;
+      pcr[3 * NT + p] = D;
+      __syncthreads();
+      const int im = p - st, ip = p + st;
+      const bool hm = im >= 0, hp = ip < FOM_THREADS;
+      const double Am = hm ? pcr[im] : 0.0, Bm = hm ? pcr[NT + im] : 1.0, Cm = hm ? pcr[2 * NT + im] : 0.0, Dm = hm ? pcr[3 * NT + im] : 0.0;
+      const double Ap = hp ? pcr[ip] : 0.0, Bp = hp ? pcr[NT + ip] : 1.0, Cp = hp ? pcr[2 * NT + ip] : 0.0, Dp = hp ? pcr[3 * NT + ip] : 0.0;
+      const double k1 = A / Bm, k2 = C / Bp;
+      const double nA = -Am * k1, nC = -Cp * k2, nB = B - Cm * k1 - Ap * k2, nD = D - Dm * k1 - Dp * k2;
+      __syncthreads();
+      A = nA, B = nB, C = nC, D = nD;
+    }
+    const double xB = D / B;
+    bad |= active && !std::isfinite(1.0 / B);
+    shb[p] = xB;
+    if (__syncthreads_or(bad) && info == 0) info = (int)(1 + g);
+
+    // ---- C: upwards inside the partition, x_k = y_k - c_k x_k+1 - f_k xL from x_last = xB, tile by tile
+    const double xL = p > 0 ? shb[p - 1] : 0.0;
+    double* out = P.U + (size_t)j * P.stride_mu + (size_t)s * P.ld_step;
+    double xnext = xB;
+    for (int k0 = (m - 1) / FOM_KT * FOM_KT; k0 >= 0; k0 -= FOM_KT) {
+      double cq[FOM_KT], fq[FOM_KT], yq[FOM_KT];
+#pragma unroll
+      for (int kk = 0; kk < FOM_KT; ++kk) {
+        const int k = k0 + kk;
+        cq[kk] = fq[kk] = yq[kk] = 0.0;
+        if (k + 1 < mp) {
+          cq[kk] = fc[k * NT + p];
+          fq[kk] = ff[k * NT + p];
+          yq[kk] = fy[k * NT + p];
+        }
+      }
+#pragma unroll
+      for (int kk = FOM_KT - 1; kk >= 0; --kk) {
+        const int k = k0 + kk;
+        if (k < mp) {
+          const double x = k + 1 == mp ? xB : yq[kk] - cq[kk] * xnext - fq[kk] * xL;
+          xnext = x;
+          S1[k * NT + p] = x;
+          tile[p * FOM_TILE_LD + kk] = x;
+        }
+      }
+      __syncthreads();
+      fom_tile_to_global(tile, out, k0, m, n);
+      __syncthreads();
+    }
+    if (p == 0) {
+      out[0] = 0.0;
+      out[P.nx] = 0.0;
+    }
+    double* t = S0;
+    S0 = S1;
+    S1 = t;
+  }
+  if (p == 0) P.info[j] = info;
+}
+
+// Argument checks and the partitioning: host logic only, shared by the entry point and the plan query.
+int fom_plan(const rt_fom_desc* d, const double* U_out, int64_t ld_step, int64_t stride_mu, const int* info, FomPlan* plan,
+             const char** why) {
+#define FOM_ARG(cond)                      \
+  do {                                     \
+    if (!(cond)) {                         \
+      *why = "bad argument: " #cond;       \
+      return RT_ERR_ARG;                   \
+    }                                      \
+  } while (0)
+  FOM_ARG(d && U_out && info);
+  FOM_ARG(d->tab);
+  FOM_ARG(d->nx >= 2 && d->n_mu >= 1 && d->nt >= 1 && d->first_step >= 0);
+  FOM_ARG(d->u_init || d->first_step == 0);
+  FOM_ARG(d->n_mu < (1L << 31) && d->nt < (1L << 40) && d->first_step < (1L << 30));
+  if (d->nx > FOM_MAX_NX) {
+    *why = "rt_p1_fom_bdf_sweep: nx > 2^22";
+    return RT_ERR_UNSUPPORTED;
+  }
+  const int64_t Nh = d->nx + 1;
+  FOM_ARG(ld_step >= Nh);
+  FOM_ARG(ld_step < (1L << 40) && stride_mu < (1L << 60) / d->n_mu);
+  FOM_ARG(d->n_mu == 1 || stride_mu >= (d->nt - 1) * ld_step + Nh);   // trajectories do not overlap
+#undef FOM_ARG
+  const long n = d->nx - 1;
+  const long m = (n + FOM_THREADS - 1) / FOM_THREADS;
+  const long parts = (n + m - 1) / m;
+  const size_t scratch = (size_t)d->n_mu * 5 * m * FOM_THREADS * 8;
+  if (scratch > FOM_MAX_SCRATCH) {
+    *why = "rt_p1_fom_bdf_sweep: more than 64 GiB of states and factors (40 KiB x ceil((nx-1)/1024) per point): sweep fewer points per call";
+    return RT_ERR_UNSUPPORTED;
+  }
+  *plan = FomPlan{m, parts, scratch};
+  return RT_OK;
+}
+
+}  // namespace
+
+int rt_p1_fom_bdf_sweep_plan_info(int num_cus, const rt_fom_desc* desc, int64_t ld_step, int64_t stride_mu, int64_t* info3) {
+  if (num_cus <= 0) return RT_ERR_ARG;
+  FomPlan plan;
+  const char* why = nullptr;
+  static const double some_out = 0.0;   // the plan query has no output buffers: the checks only see that they are not null
+  static const int some_info = 0;
+  RT_TRY(fom_plan(desc, &some_out, ld_step, stride_mu, &some_info, &plan, &why));
+  if (info3) {
+    info3[0] = desc->n_mu;
+    info3[1] = plan.parts;
+    info3[2] = plan.m;
+  }
+  return RT_OK;
+}
+
+int rt_p1_fom_bdf_sweep(rt_ctx* ctx, const rt_fom_desc* desc, double* U_out, int64_t ld_step, int64_t stride_mu, int* info) {
+  if (!ctx) return RT_ERR_ARG;
+  FomPlan plan;
+  const char* why = nullptr;
+  const int rc = fom_plan(desc, U_out, ld_step, stride_mu, info, &plan, &why);
+  if (rc != RT_OK) {
+    ctx->err = why;
+    return rc;
+  }
+  void* scratch = nullptr;
+  RT_TRY(rt_scratch(ctx, plan.scratch, &scratch));
+  FomParams p;
+  p.nx = desc->nx;
+  p.n_mu = desc->n_mu;
+  p.nt = desc->nt;
+  p.first_step = desc->first_step;
+  p.m = plan.m;
+  p.parts = plan.parts;
+  p.ld_step = ld_step;
+  p.stride_mu = stride_mu;
+  p.dt = desc->dt;
+  p.bdf2 = desc->bdf2 != 0;
+  p.state_in_w = desc->state_in_w != 0;
+  p.tab = desc->tab;
+  p.u_init = desc->u_init;
+  p.U = U_out;
+  p.info = info;
+  p.arena = static_cast<double*>(scratch);
+  RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&p1_fom_kernel), FOM_LDS_BYTES));
+  hipLaunchKernelGGL(p1_fom_kernel, dim3((unsigned)desc->n_mu), dim3(FOM_THREADS), FOM_LDS_BYTES, ctx->stream, p);
+  RT_HIP_CHECK(ctx, hipGetLastError());
+  ctx->last_grid = desc->n_mu;
+  ctx->last_splits = plan.parts;
+  ctx->last_tile = plan.m;
+  return RT_OK;
+}

@@ -480,6 +480,45 @@ def p1_local_assembly(kind: str, nx: int, rows, cols, h, coef=None, state=None, 
     return out
 
 
+def p1_fom_plan(nx: int, n_mu: int = 1, nt: int = 1, num_cus: int = 256):
+    """(workgroups, partitions per system, rows per partition) of ``p1_fom_bdf_sweep`` for nx cells - host logic only,
+    no GPU (rt_p1_fom_bdf_sweep_plan_info); raises where the sweep would refuse the sizes."""
+    lib = _lib.load()
+    Nh = int(nx) + 1
+    tab = (C.c_double * 7)()   # the checks only see that the table is there
+    desc = _lib.FomDesc(int(nx), int(n_mu), int(nt), 0, 1.0, 0, 0, C.cast(tab, _p), None)
+    info3 = (C.c_int64 * 3)()
+    rc = lib.rt_p1_fom_bdf_sweep_plan_info(int(num_cus), C.byref(desc), Nh, int(nt) * Nh, info3)
+    if rc != 0:
+        raise RomtimeHipError(f"rt_p1_fom_bdf_sweep_plan_info failed ({rc}) for nx = {nx}, n_mu = {n_mu}, nt = {nt}")
+    return int(info3[0]), int(info3[1]), int(info3[2])
+
+
+def p1_fom_bdf_sweep(nx: int, tab, dt: float, bdf2: bool, state_in_w: bool, u_init: torch.Tensor = None, first_step: int = 0):
+    """Full-order BDF sweep of a closed-form 1-D P1 model for every parameter point of ``tab`` (nt, n_mu, 7: h, alpha, c0,
+    c1, a0, a1, a2 per step and point; ``MockHeatEquation.p1_fom_recipe`` / ``MockBurgers.p1_fom_recipe``), the whole
+    time loop in one launch.  ``u_init`` (n_mu, 2, nx + 1): u^n and u^{n-1} of a sweep continued at global step
+    ``first_step``; None = zero initial state.  Returns ``(U, info)``: U (n_mu, nt, nx + 1) homogeneous snapshots - every
+    ``U[j].T`` the N_h x nt column-major snapshot matrix the POD and ``trajectory_errors`` take - and info (n_mu int32): 0,
+    or 1 + the global step at which a row lost diagonal dominance or a pivot was not finite.  rt_p1_fom_bdf_sweep."""
+    ctx = Context.current()
+    tab = to_device(tab).contiguous()
+    if tab.dim() != 3 or tab.shape[2] != 7:
+        raise RomtimeHipError("p1_fom_bdf_sweep: `tab` must be (nt, n_mu, 7)")
+    nt, n_mu, Nh = int(tab.shape[0]), int(tab.shape[1]), int(nx) + 1
+    if u_init is not None:
+        u_init = to_device(u_init).contiguous()
+        if tuple(u_init.shape) != (n_mu, 2, Nh):
+            raise RomtimeHipError(f"p1_fom_bdf_sweep: `u_init` must be (n_mu, 2, {Nh})")
+    out = torch.empty((n_mu, nt, Nh), dtype=torch.float64, device=tab.device)
+    info = torch.empty(n_mu, dtype=torch.int32, device=tab.device)
+    desc = _lib.FomDesc(int(nx), n_mu, nt, int(first_step), float(dt), int(bool(bdf2)), int(bool(state_in_w)), _ptr(tab),
+                        _ptr(u_init))
+    ctx.check(ctx.lib.rt_p1_fom_bdf_sweep(ctx.handle, C.byref(desc), _ptr(out), Nh, nt * Nh, _ptr(info)),
+              "rt_p1_fom_bdf_sweep")
+    return out, info
+
+
 def sym_eig_values(G: torch.Tensor, first: int = 0, count: int | None = None):
     """Eigenvalues (descending, device) of the symmetric n x n G; (lam, status).  With ``first`` / ``count`` only
     lam[first:first+count] is computed (the rest of ``lam`` is left unset).  rt_sym_eig_values(_part)."""

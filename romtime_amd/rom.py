@@ -47,6 +47,11 @@ class RomConstructor(Reductor):
     # produced.  The two answers differ (by up to the GMRES tolerance), so the caller chooses.
     REDUCED_SOLVER = "direct"
     GMRES_OPTIONS = dict(atol=1e-10, tol=1e-10, maxiter=1e6)
+    # Where the snapshots of ``build_reduced_basis`` come from.  "host": ``fom.solve()`` for one mu after the other, every
+    # set uploaded when it is there.  "device": one full-order sweep of the whole sampling space on the device
+    # (``romtime_amd.fom``, rt_p1_fom_bdf_sweep) for a FOM that describes itself through ``p1_fom_recipe``; its snapshots
+    # differ from the host loop's by rounding, so the caller chooses.
+    SNAPSHOTS_ON = "host"
 
     def __init__(self, fom, grid, name=None) -> None:
         super().__init__(grid=grid)
@@ -187,6 +192,29 @@ class RomConstructor(Reductor):
                     yield walks.upload(snaps)
                 if getattr(fom, "RUNTIME_PROCESS", False) and hasattr(fom, "save_probes"):
                     fom.save_probes(name=f"probes_offline_fom_{mu_idx}.csv")
+
+        def time_level_sets_device():
+            from . import fom as device_fom
+
+            mus = [self.add_mu(mu=mu, step=Stage.OFFLINE) for mu in space]
+            rec = device_fom.recipe(fom, [mu for _, mu in mus])
+            (_, U), = device_fom.fom_sweep(fom, [mu for _, mu in mus], rec=rec)
+            full = device_fom.full_solution(U, rec["lift"])
+            for j, (mu_idx, mu) in enumerate(mus):
+                fom_solutions[mu_idx] = full[j].T.cpu().numpy()
+                tags.append((mu_idx, False))
+                yield U[j].T
+                if rec["state_in_w"]:
+                    tags.append((mu_idx, True))
+                    yield device_fom.nonlinear_snapshots(fom, U[j])
+
+        if self.SNAPSHOTS_ON not in ("host", "device"):
+            raise ValueError(f"SNAPSHOTS_ON must be 'host' or 'device', not {self.SNAPSHOTS_ON!r}")
+        if self.SNAPSHOTS_ON == "device":
+            if not hasattr(fom, "p1_fom_recipe"):
+                raise NotImplementedError(f"SNAPSHOTS_ON = 'device' needs a full-order model with p1_fom_recipe(mus, ts); "
+                                          f"{type(fom).__name__} has none")
+            time_level_sets = time_level_sets_device
 
         per_mu, per_mu_nl, width = [], [], dict()
         for i, out in enumerate(walks.pod_sequence(time_level_sets(), tol=tol_t)):

@@ -269,6 +269,24 @@ class MockHeatEquation(MockSolver):
         out["lifting_poly"] = np.array([[self.lifting_poly(mu, t) for mu in mus] for t in np.asarray(ts, dtype=float)])
         return out
 
+    def p1_fom_recipe(self, mus, ts):
+        """What ``ops.p1_fom_bdf_sweep`` needs to run ``solve`` for every mu on the device: ``tab`` (nt, n_mu, 7) = h,
+        alpha, c0, c1, a0, a1, a2 per step and point - the step's matrix is mass + stiffness + the trilinear form of
+        w_i = c0 + c1 i/nx with c0 = 0 and c1 = -mesh_velocity_amplitude (the ALE ramp), its load the degree-2 rule of
+        forcing_poly - lifting_poly; ``state_in_w`` False, ``bdf2`` from BDF_SCHEME; ``lift`` (nt, n_mu, 2): the lifting
+        function on the moved mesh is g0 + g1 i/nx."""
+        ts = np.asarray(ts, dtype=float)
+        cf = self.p1_closed_form(mus, ts)
+        tab = np.zeros((ts.size, len(mus), 7))
+        tab[:, :, 0], tab[:, :, 1], tab[:, :, 3] = cf["h"], cf["alpha"], -cf["mesh_velocity"]
+        tab[:, :, 4:] = cf["forcing_poly"] - cf["lifting_poly"]
+        lift = np.empty((ts.size, len(mus), 2))
+        for s, t in enumerate(ts):
+            for j, mu in enumerate(mus):
+                bd = self.boundary_data(mu, t)
+                lift[s, j] = bd["b0"], bd["bL"] - bd["b0"]
+        return dict(tab=tab, state_in_w=False, bdf2=self.BDF_SCHEME == "2", lift=lift)
+
 
 class MockBurgers(MockSolver):
     """Burgers/piston-type operators for the online loop (rom/rom.py:877-929).
@@ -347,6 +365,19 @@ class MockBurgers(MockSolver):
         fa, fb = gdot[:-1], gdot[1:]
         elem = np.stack([h / 6.0 * (2.0 * fa + fb), h / 6.0 * (fa + 2.0 * fb)], axis=1)
         return self._assemble_vector(elem, entries)
+
+    def p1_fom_recipe(self, mus, ts):
+        """As MockHeatEquation.p1_fom_recipe: the step's matrix is bdf mass + stiffness + the trilinear form of
+        w_i = u*_i + c0 + c1 i/nx - the state (``state_in_w`` True), MockSolver's constant convection (c0 = -1) and the
+        lifting ramp (c1 = delta sin(omega t)) - and its load that of the ramp lift_dot x / L."""
+        ts = np.asarray(ts, dtype=float)
+        cf = self.p1_closed_form(mus, ts)
+        tab = np.zeros((ts.size, len(mus), 7))
+        tab[:, :, 0], tab[:, :, 1], tab[:, :, 2], tab[:, :, 3] = cf["h"], cf["alpha"], -1.0, cf["lift"]
+        tab[:, :, 5] = cf["lift_dot"] / (cf["h"] * self.nx)
+        lift = np.zeros((ts.size, len(mus), 2))
+        lift[:, :, 1] = cf["lift"]
+        return dict(tab=tab, state_in_w=True, bdf2=bool(self.bdf2), lift=lift)
 
 
 def _p1_closed_form(self, mus, ts):
