@@ -60,7 +60,9 @@ int rt_ctx_set_profile(rt_ctx* ctx, int on);
  * "sweep_graph" (default 0): rt_hrom_bdf_sweep captures one time step as a hipGraph (its kernels read the step from a
  * device counter) and replays it for steps 1 .. nt-1 instead of launching two kernels per step; for hosts that
  * cannot keep ahead of the device.  The call then returns only when the sweep has finished.  Ignored while the ctx's
- * reduced solver is RT_SOLVER_GMRES (rt_ctx_set_reduced_solver): the launches are then eager. */
+ * reduced solver is RT_SOLVER_GMRES (rt_ctx_set_reduced_solver): the launches are then eager.
+ * "pod_blocked" (default 0): rt_pod_orth takes snapshot sets of 2049 .. 16384 columns through rt_sym_eig_blocked at
+ * level 0 and at every deflated level, instead of returning RT_ERR_UNSUPPORTED. */
 int rt_ctx_set_option(rt_ctx* ctx, const char* name, int value);
 /* "cu_limit" (default 0 = the device's CU count; a multiple of 8): the number of CUs this ctx sizes its persistent grids
  * for - set it on a ctx whose stream is CU-masked (below) so that, e.g., the snapshot Gram kernel launches exactly the
@@ -84,7 +86,9 @@ int rt_last_gemm_ms(rt_ctx* ctx, double* ms);
  * another XCD than the one their K range was laid out for: should stay 0), "sweep_newton_iterations", "sweep_restarts",
  * "sweep_lu_fallbacks", "sweep_solves" (the four numbers of rt_last_sweep_stats), "sweep_gmres_iterations" (GMRES inner
  * iterations of the most recent sweep, RT_SOLVER_GMRES), "sweep_gmres_unconverged" (its systems that GMRES left with
- * info != 0).  All six sweep counters are zeroed at the start of every sweep, whatever its solver. */
+ * info != 0).  All six sweep counters are zeroed at the start of every sweep, whatever its solver.  "eig_blocked" /
+ * "eig_blocked_not_reducible" (rt_sym_eig_blocked calls that ended with status 0 / status 1) and "eig_blocked_rank" (R of
+ * the most recent of those calls: a value, not a count). */
 int rt_ctx_get_counter(rt_ctx* ctx, const char* name, int64_t* value);
 /* The same for the most recent launch of the snapshot Gram kernel (rt_gram, n >= 97, long X): its own event pair,
  * so it can be read at the end of a POD step, after the GEMMs that followed it, without holding the host back. */
@@ -113,7 +117,8 @@ int rt_gram_scale(rt_ctx* ctx, double* G, int64_t n, double* colnorm, int normal
 /* The whole of `orth` (pod.py:7-62) in one call, for hosts that bind this library without the Python layer: column
  * norms (normalize != 0), Gram matrix, all singular values, energy curve, truncation with the reference's precedence
  * (tol != 0: energy < tol, strict; else num != 0: first num; else sigma > 1e-7), basis.  X: n_rows x n_cols DEVICE matrix
- * (ld, layout), n_cols <= 2048 (RT_ERR_UNSUPPORTED beyond).  Q: DEVICE buffer n_rows x q_cols row-major; on return its first *r_out columns are the
+ * (ld, layout), n_cols <= 2048 (RT_ERR_UNSUPPORTED beyond; with the ctx option "pod_blocked" n_cols <= 16384, every level's
+ * eigensolve through rt_sym_eig_blocked, and RT_ERR_UNSUPPORTED where that reports a set that is not reducible).  Q: DEVICE buffer n_rows x q_cols row-major; on return its first *r_out columns are the
  * basis (the others are zero or unspecified); if the rule keeps more than q_cols modes the call returns RT_ERR_ARG with
  * *r_out = the number needed.  s_host / energy_host: HOST arrays of min(n_rows, n_cols) entries - ALL singular values and
  * the whole energy curve, as the reference returns them.  *levels_out (may be NULL): Gram passes taken (1 = single pass;
@@ -476,6 +481,39 @@ int rt_sym_eig_vectors(rt_ctx* ctx, int64_t n, int64_t k, const double* lam, dou
  * POD (romtime_amd/pod.py, passes=2). */
 int rt_sym_jacobi_eigh(rt_ctx* ctx, const double* A, int64_t n, double* lam, double* W, int max_sweeps, int* sweeps_done,
                        int* status);
+
+/* ---- Gram matrices of 2049 .. 16384 snapshots: block Rayleigh-Ritz (since version 400; the eigenvalue half of
+ *      scipy.linalg.svd, pod.py:38, for sets wider than the eigensolver above takes) ---------- */
+/* The partition rule, host logic only: p = ceil(n / block_max) contiguous blocks whose widths differ by at most one, the
+ * wider ones first (widths[b] = n / p + (b < n % p)).  *p_out = p; widths (p entries, may be NULL).  n < 1, block_max < 1
+ * or a null p_out return RT_ERR_ARG, p > 8 RT_ERR_UNSUPPORTED (16384 = 8 x 2048). */
+int rt_sym_eig_blocked_plan_info(int64_t n, int64_t block_max, int64_t* p_out, int64_t* widths);
+#define RT_EIG_BLOCKED_OK 0
+#define RT_EIG_BLOCKED_NOT_REDUCIBLE 1
+#define RT_EIG_BLOCKED_SOLVE_FAILED 2
+/* Leading eigenpairs of a symmetric positive semi-definite G (n x n row-major DEVICE matrix, not modified), 2048 < n <=
+ * 16384, whose spectrum decays (a snapshot Gram matrix).  The diagonal blocks of the partition above (block_max = 2048)
+ * go through rt_sym_eig_values / rt_sym_eig_vectors one after the other; block b keeps the rho_b eigenvectors W_b whose
+ * eigenvalue exceeds floor_rel * lam_max, lam_max the largest block eigenvalue of all; with W = blockdiag(W_b) (n x R, R =
+ * sum rho_b) the R x R matrix G_M = (W^T G W + its transpose) / 2 goes through the same eigensolver (closed form for R <= 2)
+ * and its eigenpairs (theta, Y) give the Ritz pairs (theta, W Y) of G:  0 <= lam_i(G) - theta_i <= p floor_rel lam_max in
+ * exact arithmetic ("Block Rayleigh-Ritz").
+ *   - lam (n, DEVICE): the R Ritz values, descending, then zeros.  W (DEVICE, n x min(k, R) row-major, leading dimension
+ *     min(k, R); may be NULL when k = 0): column t pairs with lam[t].
+ *   - resolved (HOST, 1 entry) = R; block_ranks (HOST, p entries) = rho_b; status (HOST int) = RT_EIG_BLOCKED_OK,
+ *     RT_EIG_BLOCKED_NOT_REDUCIBLE when R > 2048 (lam and W are left untouched, block_ranks and resolved are filled, the
+ *     call returns RT_OK; the pass over the blocks ends as soon as the eigenvalues above floor_rel max_b trace(G_bb), an
+ *     upper bound of the floor, pass 2048, and block_ranks / resolved are then those lower bounds), or
+ *     RT_EIG_BLOCKED_SOLVE_FAILED when an eigensolve reported a nonzero status of its own (a hand-off time-out: that
+ *     status is 1 as well, hence a value of its own here; results invalid, the call returns RT_OK).
+ *   - 2048 < n <= 16384, floor_rel > 0, 0 <= k <= n; n <= 2048 returns RT_ERR_ARG (rt_sym_eig_values takes those), n >
+ *     16384 RT_ERR_UNSUPPORTED.
+ *   - Synchronises the ctx stream (every block's spectrum is read on the host).  Work memory is taken from the device's
+ *     stream-ordered pool for the duration of the call, the eigensolves use the ctx arenas as they always do.  No
+ *     floating-point atomics, and every grid depends on the sizes alone.
+ *   - Counters "eig_blocked", "eig_blocked_not_reducible", "eig_blocked_rank". */
+int rt_sym_eig_blocked(rt_ctx* ctx, const double* G, int64_t n, double floor_rel, int64_t k, double* lam, double* W,
+                       int64_t* resolved, int64_t* block_ranks, int* status);
 
 /* ---- host-side small dense step --------------------------------------------------------- */
 /* Cyclic two-sided Jacobi eigen-decomposition of a symmetric PSD n x n HOST matrix A (row-major,

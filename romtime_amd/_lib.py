@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libromtime_hip.so")
 ROW_MAJOR, COL_MAJOR = 0, 1
 RT_OK = 0
 WARN_ZERO_NORM, WARN_SINGULAR = 1, 2
+EIG_BLOCKED_OK, EIG_BLOCKED_NOT_REDUCIBLE, EIG_BLOCKED_SOLVE_FAILED = 0, 1, 2   # status of rt_sym_eig_blocked
 
 _p = C.c_void_p
 _i64 = C.c_int64
@@ -84,6 +85,8 @@ SIGNATURES = {
     "rt_sym_eig_values": (_int, [_p, _p, _i64, _p, _p]),
     "rt_sym_eig_values_part": (_int, [_p, _p, _i64, _i64, _i64, _p, _p]),
     "rt_sym_eig_vectors": (_int, [_p, _i64, _i64, _p, _p]),
+    "rt_sym_eig_blocked_plan_info": (_int, [_i64, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
+    "rt_sym_eig_blocked": (_int, [_p, _p, _i64, C.c_double, _i64, _p, _p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_int)]),
     "rt_sym_jacobi_eigh": (_int, [_p, _p, _i64, _p, _p, _int, C.POINTER(_int), _p]),
     "rt_host_jacobi_eigh": (_int, [_p, _i64, _p, _p, _int, C.POINTER(_int)]),
     "rt_bench_mfma_f64": (_int, [_p, _int, C.POINTER(C.c_double)]),

@@ -187,7 +187,7 @@ int rt_profile_end(rt_ctx* ctx, bool also_gram) {
 
 extern "C" {
 
-int rt_version(void) { return 390; }  // 390: rt_p1_fom_bdf_sweep (full-order BDF sweeps of the closed-form P1 models), rt_p1_fom_bdf_sweep_plan_info; 380: rt_interpolation_errors ((M)DEIM interpolation errors of whole snapshot sets), rt_interpolation_errors_plan_info; 370: rt_trajectory_integrals (mass and other integrals of whole trajectories), rt_trajectory_integrals_plan_info; 360: rt_sym_jacobi_eigh (device Jacobi for the two-pass POD); 350: rt_sym_eig_* and rt_pod_orth take n <= 2048 (wide tridiagonalisation), counter eig_wide_form; 340: rt_trajectory_errors; 330: rt_gmres_batched, rt_ctx_set_reduced_solver, counters sweep_gmres_*; 320: rt_gram_plan_info; 310: option gram_pace (paced / one-launch Gram); 300 (round 3): rt_dense_solve_multi, RT_P1_LOAD_P2; 210: rt_tracked_solve_batched, rt_pod_enqueue, options eig_xcd, counter gram_off_xcd
+int rt_version(void) { return 400; }  // 400: rt_sym_eig_blocked (block Rayleigh-Ritz on Gram matrices of 2049 .. 16384 snapshots), rt_sym_eig_blocked_plan_info, option pod_blocked, counters eig_blocked*; 390: rt_p1_fom_bdf_sweep (full-order BDF sweeps of the closed-form P1 models), rt_p1_fom_bdf_sweep_plan_info; 380: rt_interpolation_errors ((M)DEIM interpolation errors of whole snapshot sets), rt_interpolation_errors_plan_info; 370: rt_trajectory_integrals (mass and other integrals of whole trajectories), rt_trajectory_integrals_plan_info; 360: rt_sym_jacobi_eigh (device Jacobi for the two-pass POD); 350: rt_sym_eig_* and rt_pod_orth take n <= 2048 (wide tridiagonalisation), counter eig_wide_form; 340: rt_trajectory_errors; 330: rt_gmres_batched, rt_ctx_set_reduced_solver, counters sweep_gmres_*; 320: rt_gram_plan_info; 310: option gram_pace (paced / one-launch Gram); 300 (round 3): rt_dense_solve_multi, RT_P1_LOAD_P2; 210: rt_tracked_solve_batched, rt_pod_enqueue, options eig_xcd, counter gram_off_xcd
 
 int rt_ctx_create(rt_ctx** out, int device) {
   if (!out) return RT_ERR_ARG;
@@ -296,6 +296,10 @@ int rt_ctx_set_option(rt_ctx* ctx, const char* name, int value) {
     ctx->gram_pace_on = value != 0;
     return RT_OK;
   }
+  if (key == "pod_blocked") {
+    ctx->pod_blocked = value != 0;
+    return RT_OK;
+  }
   if (key == "sweep_graph") {
     ctx->sweep_graph = value != 0;
     return RT_OK;
@@ -320,7 +324,8 @@ int rt_ctx_get_counter(rt_ctx* ctx, const char* name, int64_t* value) {
       {"eig_one_xcd", RT_CNT_EIG_ONE_XCD}, {"gram_off_xcd", RT_CNT_GRAM_OFF_XCD}, {"sweep_newton_iterations", RT_CNT_NS_ITER},
       {"sweep_restarts", RT_CNT_NS_RESTART}, {"sweep_lu_fallbacks", RT_CNT_LU_FALLBACK}, {"sweep_solves", RT_CNT_SOLVES},
       {"sweep_gmres_iterations", RT_CNT_GMRES_ITER}, {"sweep_gmres_unconverged", RT_CNT_GMRES_UNCONVERGED},
-      {"eig_wide_form", RT_CNT_EIG_WIDE_FORM}};
+      {"eig_wide_form", RT_CNT_EIG_WIDE_FORM}, {"eig_blocked", RT_CNT_EIG_BLOCKED},
+      {"eig_blocked_not_reducible", RT_CNT_EIG_BLOCKED_NOT_REDUCIBLE}, {"eig_blocked_rank", RT_CNT_EIG_BLOCKED_RANK}};
   for (const auto& t : table)
     if (key == t.name) {
       long host = 0;

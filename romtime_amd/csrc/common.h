@@ -11,7 +11,7 @@
 typedef double d2 __attribute__((ext_vector_type(2)));
 typedef double d4 __attribute__((ext_vector_type(4)));
 
-constexpr int RT_N_COUNTERS = 11;
+constexpr int RT_N_COUNTERS = 14;
 
 struct rt_ctx {
   int device = 0;
@@ -48,6 +48,7 @@ struct rt_ctx {
   // started}, 128 B apart); zeroed when allocated and again by every Gram's reduction kernel
   unsigned long long* gram_pace = nullptr;
   bool gram_pace_on = true;         // "gram_pace" option
+  bool pod_blocked = false;         // "pod_blocked" option: rt_pod_orth takes n_cols > 2048 through rt_sym_eig_blocked
   int reduced_solver = RT_SOLVER_DIRECT;      // what the two sweeps solve their systems with (rt_ctx_set_reduced_solver)
   rt_gmres_opts gmres_opts{1e-5, 0.0, 20, 1}; // ... and the options of RT_SOLVER_GMRES
 };
@@ -64,7 +65,10 @@ enum {
   RT_CNT_SOLVES = 7,            // ... systems solved
   RT_CNT_GMRES_ITER = 8,        // ... GMRES inner iterations (RT_SOLVER_GMRES)
   RT_CNT_GMRES_UNCONVERGED = 9, // ... systems GMRES left with info != 0
-  RT_CNT_EIG_WIDE_FORM = 10     // tridiagonalisations that took the wide route (1024 < n <= 2048, one launch per dependency)
+  RT_CNT_EIG_WIDE_FORM = 10,    // tridiagonalisations that took the wide route (1024 < n <= 2048, one launch per dependency)
+  RT_CNT_EIG_BLOCKED = 11,      // rt_sym_eig_blocked calls that returned Ritz pairs (status 0)
+  RT_CNT_EIG_BLOCKED_NOT_REDUCIBLE = 12,  // ... that found more than 2048 block eigenvalues above the floor (status 1)
+  RT_CNT_EIG_BLOCKED_RANK = 13  // R of the most recent rt_sym_eig_blocked call (a value, not a count)
 };
 
 #define RT_TRY(expr)                 \

@@ -63,6 +63,8 @@ struct Eig {                  // eigen-decomposition of one level's Gram matrix
   double* lam_d = nullptr;    // device copy (n), valid when on_device
   bool on_device = false;
   std::vector<double> W_host; // n x n eigenvectors (columns), host route only
+  bool blocked = false;       // n > 2048: Ritz pairs of rt_sym_eig_blocked; Z holds the first `resolved` Ritz vectors
+  int resolved = 0;
 };
 
 // One rt_pod_orth call: its sizes and its small persistent device buffers.  hipMallocAsync keeps them off the ctx arenas,
@@ -97,6 +99,28 @@ int eigensolve(Pod& p, const double* Gm, Eig& e) {
   int* flags = p.flags;
   e.lam.assign(n, 0.0);
   e.on_device = (n >= 3);
+  e.blocked = false;
+  if (n > 2048) {
+    // the block Rayleigh-Ritz route ("pod_blocked"): Ritz values (zeros beyond R) and all R Ritz vectors at once, into Z
+    int64_t R = 0, ranks[8];
+    int status = 0;
+    RT_TRY(rt_sym_eig_blocked(ctx, Gm, n, n * 2.220446049250313e-16, n, lam_d, p.Z, &R, ranks, &status));
+    if (status == RT_EIG_BLOCKED_NOT_REDUCIBLE) {
+      ctx->err = "rt_pod_orth: the snapshot set is not reducible (more than 2048 block eigenvalues above n eps lam_max: "
+                 "rt_sym_eig_blocked); use the pieces with a host eigensolver";
+      return RT_ERR_UNSUPPORTED;
+    }
+    if (status != 0) {
+      ctx->err = "rt_pod_orth: an eigensolve of rt_sym_eig_blocked timed out";
+      return RT_ERR_HIP;
+    }
+    RT_HIP_CHECK(ctx, hipMemcpyAsync(e.lam.data(), lam_d, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    RT_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    e.lam_d = lam_d;
+    e.blocked = true;
+    e.resolved = (int)R;
+    return RT_OK;
+  }
   if (e.on_device) {
     RT_TRY(rt_sym_eig_values(ctx, Gm, n, lam_d, flags + 1));
     int status = 0;
@@ -137,34 +161,50 @@ int eigenvectors(Pod& p, const double* Gm, Eig& e, int k) {
     RT_HIP_CHECK(ctx, hipStreamSynchronize(st));
     return RT_OK;
   }
-  RT_TRY(rt_sym_eig_vectors(ctx, n, k, e.lam_d, Z));
-  if (rt_separated(e.lam, k)) return RT_OK;
+  int kc = k;   // the columns that hold vectors: all k, but min(k, R) on the blocked route (leading dimension k either way)
+  if (e.blocked) {
+    // Z holds the R Ritz vectors with leading dimension R: compact the first min(k, R) columns to leading dimension k,
+    // zero columns beyond R (their Ritz values are zero, and so are their modes)
+    const int R = e.resolved;
+    kc = std::min(k, R);
+    double* tmp = p.Zs;  // free at this point
+    RT_HIP_CHECK(ctx, hipMemsetAsync(tmp, 0, sizeof(double) * (size_t)n * k, st));
+    if (kc > 0)
+      RT_HIP_CHECK(ctx, hipMemcpy2DAsync(tmp, sizeof(double) * k, Z, sizeof(double) * R, sizeof(double) * kc, n,
+                                         hipMemcpyDeviceToDevice, st));
+    RT_HIP_CHECK(ctx, hipMemcpyAsync(Z, tmp, sizeof(double) * (size_t)n * k, hipMemcpyDeviceToDevice, st));
+    e.blocked = false;   // Z no longer holds the R vectors: a level asks for its vectors once
+    if (kc == 0) return RT_OK;
+  } else {
+    RT_TRY(rt_sym_eig_vectors(ctx, n, k, e.lam_d, Z));
+  }
+  if (rt_separated(e.lam, kc)) return RT_OK;
   // clustered: H = Z^T G Z, S = Z^T Z, H c = theta S c on the host, Z <- Z C
-  double* GZ = p.Zs;  // free at this point
-  RT_TRY(rt_gemm_nn(ctx, Gm, n, RT_ROW_MAJOR, Z, k, n, n, k, GZ, k, RT_ROW_MAJOR));
-  RT_TRY(rt_gemm_tn(ctx, Z, k, RT_ROW_MAJOR, GZ, k, RT_ROW_MAJOR, n, k, k, small, k));
-  RT_TRY(rt_gemm_tn(ctx, Z, k, RT_ROW_MAJOR, Z, k, RT_ROW_MAJOR, n, k, k, small + (size_t)k * k, k));
-  std::vector<double> H((size_t)k * k), S((size_t)k * k), Cm, theta;
-  RT_HIP_CHECK(ctx, hipMemcpyAsync(H.data(), small, sizeof(double) * k * k, hipMemcpyDeviceToHost, st));
-  RT_HIP_CHECK(ctx, hipMemcpyAsync(S.data(), small + (size_t)k * k, sizeof(double) * k * k, hipMemcpyDeviceToHost, st));
+  double* GZ = p.Zs;  // free at this point (on the blocked route its columns beyond kc are zero, and stay so)
+  RT_TRY(rt_gemm_nn(ctx, Gm, n, RT_ROW_MAJOR, Z, k, n, n, kc, GZ, k, RT_ROW_MAJOR));
+  RT_TRY(rt_gemm_tn(ctx, Z, k, RT_ROW_MAJOR, GZ, k, RT_ROW_MAJOR, n, kc, kc, small, kc));
+  RT_TRY(rt_gemm_tn(ctx, Z, k, RT_ROW_MAJOR, Z, k, RT_ROW_MAJOR, n, kc, kc, small + (size_t)kc * kc, kc));
+  std::vector<double> H((size_t)kc * kc), S((size_t)kc * kc), Cm, theta;
+  RT_HIP_CHECK(ctx, hipMemcpyAsync(H.data(), small, sizeof(double) * kc * kc, hipMemcpyDeviceToHost, st));
+  RT_HIP_CHECK(ctx, hipMemcpyAsync(S.data(), small + (size_t)kc * kc, sizeof(double) * kc * kc, hipMemcpyDeviceToHost, st));
   RT_HIP_CHECK(ctx, hipStreamSynchronize(st));
-  for (int i = 0; i < k; ++i)
-    for (int j = i + 1; j < k; ++j) {
-      H[(size_t)i * k + j] = H[(size_t)j * k + i] = 0.5 * (H[(size_t)i * k + j] + H[(size_t)j * k + i]);
-      S[(size_t)i * k + j] = S[(size_t)j * k + i] = 0.5 * (S[(size_t)i * k + j] + S[(size_t)j * k + i]);
+  for (int i = 0; i < kc; ++i)
+    for (int j = i + 1; j < kc; ++j) {
+      H[(size_t)i * kc + j] = H[(size_t)j * kc + i] = 0.5 * (H[(size_t)i * kc + j] + H[(size_t)j * kc + i]);
+      S[(size_t)i * kc + j] = S[(size_t)j * kc + i] = 0.5 * (S[(size_t)i * kc + j] + S[(size_t)j * kc + i]);
     }
-  if (!rt_small_generalised_eigh(H, S, k, Cm, theta)) {
+  if (!rt_small_generalised_eigh(H, S, kc, Cm, theta)) {
     ctx->err = "rt_pod_orth: the Rayleigh-Ritz overlap matrix is not positive definite";
     return RT_ERR_HIP;
   }
   double worst = 0.0;
-  for (int i = 0; i < k; ++i) worst = std::max(worst, std::fabs(theta[i] - e.lam[i]));
+  for (int i = 0; i < kc; ++i) worst = std::max(worst, std::fabs(theta[i] - e.lam[i]));
   if (worst > 1e-9 * std::max(e.lam[0], 1e-300)) {
     ctx->err = "rt_pod_orth: device eigenvectors failed the Rayleigh-Ritz cross-check";
     return RT_ERR_HIP;
   }
-  RT_HIP_CHECK(ctx, hipMemcpyAsync(small, Cm.data(), sizeof(double) * k * k, hipMemcpyHostToDevice, st));
-  RT_TRY(rt_gemm_nn(ctx, Z, k, RT_ROW_MAJOR, small, k, n, k, k, GZ, k, RT_ROW_MAJOR));
+  RT_HIP_CHECK(ctx, hipMemcpyAsync(small, Cm.data(), sizeof(double) * kc * kc, hipMemcpyHostToDevice, st));
+  RT_TRY(rt_gemm_nn(ctx, Z, k, RT_ROW_MAJOR, small, kc, n, kc, kc, GZ, k, RT_ROW_MAJOR));
   RT_HIP_CHECK(ctx, hipMemcpyAsync(Z, GZ, sizeof(double) * n * k, hipMemcpyDeviceToDevice, st));
   RT_HIP_CHECK(ctx, hipStreamSynchronize(st));   // Cm is on this stack frame
   return RT_OK;
@@ -221,7 +261,7 @@ extern "C" int rt_pod_orth(rt_ctx* ctx, const double* X, int64_t n_rows, int64_t
   RT_ARG_CHECK(ctx, X && Q && r_out && s_host && energy_host && n_rows >= 1 && n_cols >= 1 && q_cols >= 0 && num >= 0);
   RT_ARG_CHECK(ctx, layout == RT_ROW_MAJOR || layout == RT_COL_MAJOR);
   RT_ARG_CHECK(ctx, ld >= (layout == RT_ROW_MAJOR ? n_cols : n_rows));
-  if (n_cols > 2048) {
+  if (n_cols > 2048 && !(ctx->pod_blocked && n_cols <= 16384)) {
     ctx->err = "rt_pod_orth: more than 2048 snapshots (the device eigensolver's limit; use the pieces with a host eigensolver)";
     return RT_ERR_UNSUPPORTED;
   }
@@ -274,7 +314,16 @@ extern "C" int rt_pod_orth(rt_ctx* ctx, const double* X, int64_t n_rows, int64_t
   const std::vector<double> s = rt_sigma(eig.lam);
   std::vector<double> energy;
   double total = 0.0;   // the energy denominator of every level
-  for (int i = 0; i < n; ++i) total += s[i] * s[i];
+  if (eig.blocked) {
+    // the Ritz values stop at R: the energy stays over trace(G), which their sum misses by the discarded block energy
+    std::vector<double> diag(n);
+    RT_HIP_CHECK(ctx, hipMemcpy2DAsync(diag.data(), sizeof(double), p.G, sizeof(double) * (n + 1), sizeof(double), n,
+                                       hipMemcpyDeviceToHost, st));
+    RT_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    for (int i = 0; i < n; ++i) total += diag[i];
+  } else {
+    for (int i = 0; i < n; ++i) total += s[i] * s[i];
+  }
   rt_energy(s, total, energy);
   int r = rt_truncation_rank(s, energy, num, tol);
   if (levels_out) *levels_out = 1;

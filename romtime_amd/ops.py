@@ -543,6 +543,54 @@ def sym_eig_vectors(lam: torch.Tensor, k: int, first: int = 0) -> torch.Tensor:
     return W
 
 
+def sym_eig_blocked_plan(n: int, block_max: int = 2048):
+    """Block widths of ``sym_eig_blocked`` for n columns - host logic only, no GPU (rt_sym_eig_blocked_plan_info); raises
+    where the library refuses the sizes.  ``pod_rules.block_partition`` states the same rule in NumPy."""
+    lib = _lib.load()
+    p = C.c_int64(0)
+    widths = (C.c_int64 * 8)()
+    rc = lib.rt_sym_eig_blocked_plan_info(int(n), int(block_max), C.byref(p), widths)
+    if rc != 0:
+        raise RomtimeHipError(f"rt_sym_eig_blocked_plan_info failed ({rc}) for n = {n}, block_max = {block_max}")
+    return np.array(widths[: p.value], dtype=np.int64)
+
+
+def sym_eig_blocked(G: torch.Tensor, k: int, floor_rel: float = None, lam: torch.Tensor = None, W: torch.Tensor = None):
+    """Leading eigenpairs of a symmetric positive semi-definite n x n G with a decaying spectrum, 2048 < n <= 16384, by
+    the block Rayleigh-Ritz route (rt_sym_eig_blocked): ``(lam, W, info)`` with ``lam`` (n, device) the R Ritz values in
+    descending order and zeros beyond, ``W`` (n x min(k, R), device) their vectors, and ``info`` a dict of ``status`` (0;
+    1: more than 2048 block eigenvalues above the floor - the set is not reducible, ``lam`` and ``W`` are None unless the
+    caller passed buffers, which are left untouched; 2: an eigensolve timed out), ``resolved`` (R) and ``block_ranks``.
+    ``floor_rel`` None = ``pod_rules.blocked_floor(n)`` = n eps.  ``lam`` / ``W``: buffers to write into instead (W: n x k;
+    the library writes n x min(k, R) with leading dimension min(k, R), so pass one only where k <= R is known).
+    Synchronises the stream."""
+    ctx = Context.current()
+    n = G.shape[0]
+    if G.dtype != torch.float64 or not G.is_cuda or G.dim() != 2 or G.shape != (n, n) or not G.is_contiguous():
+        raise RomtimeHipError("sym_eig_blocked: expected a contiguous square float64 CUDA tensor")
+    k = int(k)
+    floor_rel = pod_rules.blocked_floor(n) if floor_rel is None else float(floor_rel)
+    own = lam is None
+    lam = torch.empty(n, dtype=torch.float64, device=G.device) if lam is None else lam
+    Wbuf = torch.empty((n, k), dtype=torch.float64, device=G.device) if (W is None and k > 0) else W
+    resolved, status = C.c_int64(0), C.c_int(0)
+    ranks = (C.c_int64 * 8)()
+    ctx.check(ctx.lib.rt_sym_eig_blocked(ctx.handle, _ptr(G), n, floor_rel, k, _ptr(lam), _ptr(Wbuf), C.byref(resolved), ranks,
+                                         C.byref(status)), "rt_sym_eig_blocked")
+    R = int(resolved.value)
+    info = dict(status=int(status.value), resolved=R,
+                block_ranks=[int(ranks[b]) for b in range(len(pod_rules.block_partition(n)))])
+    if info["status"] != 0:
+        return (None, None, info) if own else (lam, W, info)
+    kk = min(k, R)
+    if W is None:
+        # the library wrote n x kk with leading dimension kk into the front of the buffer
+        Wout = Wbuf.reshape(-1)[: n * kk].view(n, kk) if k > 0 else torch.empty((n, 0), dtype=torch.float64, device=G.device)
+    else:
+        Wout = W
+    return lam, Wout, info
+
+
 def sym_jacobi_eigh(G: torch.Tensor, max_sweeps: int = 60):
     """(lam, W, sweeps) of the symmetric n x n G (n <= 2048, not modified) by two-sided Jacobi on the device: ``lam``
     descending (device), eigenvectors in the columns of ``W`` (device, n x n), ``sweeps`` the sweeps run (the closing

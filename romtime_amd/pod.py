@@ -8,7 +8,8 @@ Algorithm (device work through the C ABI, see include/romtime_hip.h):
   pass 1   G = X^T X                        rt_gram        (FP64 MFMA; the only O(N n^2) step)
            [row-sharded X: all-reduce G over RCCL/xGMI here]
            colnorm = sqrt(diag G), G <- D^-1 G D^-1        rt_gram_scale  (normalize=True, pod.py:31-33)
-           G = W L W^T                      rt_sym_eig_values / _vectors (device; host LAPACK for n > 2048)
+           G = W L W^T                      rt_sym_eig_values / _vectors (device; n > 2048: host LAPACK, or with
+                                            WIDE_EIG = "device" the block Rayleigh-Ritz route rt_sym_eig_blocked)
            sigma = sqrt(L), energy, truncation -> r
            Q = X (D^-1 W_r S_r^-1)          rt_gemm_nn     (back-projection)
 
@@ -44,6 +45,17 @@ from .pod_rules import energy as _energy
 
 DEVICE_EIG = True      # small eigenproblem on the device (rt_sym_eig_*); False = host LAPACK
 DEVICE_EIG_MAX_N = 2048  # rt_sym_eig_*: LDS-resident tridiagonalisation to 1024, the wide route (one launch per dependency) to 2048
+# Gram matrices of more than DEVICE_EIG_MAX_N snapshots: "host" = host LAPACK, as ever; "device" = the block Rayleigh-Ritz
+# route (ops.sym_eig_blocked, DESIGN.md "Block Rayleigh-Ritz") for CUDA tensors of up to BLOCKED_EIG_MAX_N columns on one
+# rank - a set it reports as not reducible takes the host route and counts in "eig_blocked_not_reducible"
+WIDE_EIG = "host"
+BLOCKED_EIG_MAX_N = 16384
+
+
+def _wide_eig() -> str:
+    if WIDE_EIG not in ("host", "device"):
+        raise ValueError(f'romtime_amd.pod.WIDE_EIG must be "host" or "device", not {WIDE_EIG!r}')
+    return WIDE_EIG
 
 
 # shapes (n, num, normalize) whose last POD could not use the work enqueued ahead of the eigenvalues (pod_device)
@@ -145,7 +157,10 @@ class _SmallEig:
     """Eigen-decomposition of the n x n Gram matrix: all eigenvalues (host array, descending) at once,
     leading eigenvectors on request (device, n x k).  3 <= n <= DEVICE_EIG_MAX_N (2048) runs on the device
     (rt_sym_eig_values / rt_sym_eig_vectors, Rayleigh-Ritz polish on G when the kept eigenvalues are
-    not ``pod_rules.separated``); other sizes use host LAPACK.  ``head``: the parsed pod_rules.Head."""
+    not ``pod_rules.separated``); other sizes use host LAPACK - or, with ``WIDE_EIG = "device"``, CUDA tensors of 2049 ..
+    BLOCKED_EIG_MAX_N columns on one rank the block Rayleigh-Ritz route (``_blocked``): ``lam`` then holds the R Ritz
+    values and zeros beyond, the vectors are the Ritz vectors, ``trace`` the energy denominator.  ``head``: the parsed
+    pod_rules.Head."""
 
     def __init__(self, G: torch.Tensor, extra=(), group=None, ahead=None):
         """``ahead(self)``: device work the caller wants enqueued BEFORE the eigenvalues reach the host (it may
@@ -154,7 +169,13 @@ class _SmallEig:
         self.on_device = bool(G.is_cuda and DEVICE_EIG and 3 <= self.n <= DEVICE_EIG_MAX_N)
         self.group = group if (group is not None and self.on_device and _world(group) > 1) else None
         self._raw = {}
-        if self.on_device:
+        self.trace = None     # the blocked route alone: trace(G), the energy denominator its Ritz values do not sum to
+        self._ritz = None     # ... and its n x R Ritz vectors
+        wide = _wide_eig()    # a bad value raises whatever the size
+        if (wide == "device" and G.is_cuda and DEVICE_EIG and DEVICE_EIG_MAX_N < self.n <= BLOCKED_EIG_MAX_N
+                and (group is None or _world(group) == 1)):
+            self._blocked(extra, ahead)
+        if self.on_device and self._ritz is None:
             if self.group is None:
                 self.lam_d, status = ops.sym_eig_values(G)
             else:
@@ -199,11 +220,44 @@ class _SmallEig:
             self.lam, self.W = _eigh_desc(Gh)
             self.head = pod_rules.parse_head(np.concatenate([self.lam, [0.0]] + extra), self.n)
 
+    def _blocked(self, extra, ahead):
+        """The block Rayleigh-Ritz route: Ritz values (zeros beyond R) for ``lam``, all R Ritz vectors kept for
+        ``raw_vectors``.  Leaves ``_ritz`` None - and the host route to take over - where the set is not reducible or an
+        eigensolve timed out twice; the library counts the former, both are warned about."""
+        import warnings
+
+        ctx = _lib.Context.current()
+        lam_d, WY, info = ops.sym_eig_blocked(self.G, self.n)
+        if info["status"] == _lib.EIG_BLOCKED_SOLVE_FAILED and ctx.options.get("eig_one_xcd", 1):
+            warnings.warn("romtime_amd: eigensolver hand-off timed out in the one-XCD form; this context now uses the "
+                          "general form (rt_ctx_set_option eig_one_xcd=0)", RuntimeWarning)
+            ctx.set_option("eig_one_xcd", 0)
+            lam_d, WY, info = ops.sym_eig_blocked(self.G, self.n)
+        if info["status"] != 0:
+            why = ("is not reducible (block ranks %s)" % info["block_ranks"] if info["status"] == _lib.EIG_BLOCKED_NOT_REDUCIBLE
+                   else "hit a hand-off time-out")
+            warnings.warn(f"romtime_amd: the block Rayleigh-Ritz eigensolve of {self.n} snapshots {why}; host LAPACK "
+                          "takes this eigenproblem", RuntimeWarning)
+            return
+        self.on_device, self.lam_d, self._ritz, self.resolved = True, lam_d, WY, info["resolved"]
+        status = torch.zeros(1, dtype=torch.int32, device=self.G.device)
+        head = pack_head(lam_d, status, *extra, self.G.diagonal().sum().reshape(1))
+        head = head.cpu().numpy() if ahead is None else _fetch_beside(head, lambda: ahead(self))
+        self.trace = float(head[-1])
+        self.head = pod_rules.parse_head(head[:-1], self.n)
+        self.lam = self.head.lam
+
     def raw_vectors(self, k: int) -> torch.Tensor:
         """Inverse-iteration eigenvectors of the k largest eigenvalues as the device computes them (no host data
         needed: usable before the eigenvalues have been fetched).  Cached per k."""
         if k in self._raw:
             return self._raw[k]
+        if self._ritz is not None:   # the blocked route: the Ritz vectors are there; zero columns beyond R
+            R = self._ritz.shape[1]
+            Z = self._ritz[:, :k].contiguous() if k <= R else torch.cat(
+                [self._ritz, self._ritz.new_zeros((self.n, k - R))], dim=1)
+            self._raw[k] = Z
+            return Z
         if self.group is None:
             Z = ops.sym_eig_vectors(self.lam_d, k)
         else:  # each rank back-transforms its share of the k vectors
@@ -230,6 +284,10 @@ class _SmallEig:
         if not self.on_device:
             return ops.to_device(np.ascontiguousarray(self.W[:, :k]), self.G.device)
         Z = self.raw_vectors(k)
+        if self._ritz is not None and k > self._ritz.shape[1]:
+            # beyond R there are no vectors to repair: the step sees the R Ritz vectors, the zero columns stay
+            R = self._ritz.shape[1]
+            return torch.cat([self.vectors(R), Z[:, R:]], dim=1) if R > 0 else Z
         if self.well_separated(k):
             return Z
         GZ = ops.gemm_nn(self.G, Z)
@@ -364,7 +422,8 @@ def pod_device(X: torch.Tensor, num=None, tol=None, normalize=True, passes=None,
     if normalize and eig.head.zero_norm != 0:
         raise pod_rules.zero_norm_error()
     s = pod_rules.sigma(eig.lam)
-    energy = _energy(s)
+    # the Ritz values of the blocked route stop at R: the energy stays over trace(G)
+    energy = _energy(s) if eig.trace is None else np.cumsum(np.power(s, 2)) / eig.trace
     r = truncation_rank(s, energy, num=num, tol=tol)
     if passes is None:
         passes = "deflate" if pod_rules.deep(s, r) else 1
@@ -438,7 +497,8 @@ def _pod_deflated(X, eig0, colnorm, normalize, num, tol, group, want_vt):
     (sigma_i gap), dgesvd's own level (POD accuracy)."""
     n = X.shape[1]
     dev = X.device
-    total = float(np.sum(np.clip(eig0.lam, 0.0, None)))   # == trace(G0): the energy denominator
+    # == trace(G0): the energy denominator (the blocked route, whose Ritz values stop at R, brings the trace itself)
+    total = float(np.sum(np.clip(eig0.lam, 0.0, None))) if eig0.trace is None else eig0.trace
     Xc, eig = None, eig0
     s_acc, Q_acc, W_acc = [], [], []
     # with ``num`` alone the basis never has more than num columns: the levels write straight into it

@@ -117,3 +117,26 @@ def parse_head(head, n, n_rows=None) -> Head:
 def zero_norm_error() -> ValueError:
     # the reference divides by a zero norm and scipy.linalg.svd then rejects the NaNs (pod.py:32-38)
     return ValueError("array must not contain infs or NaNs (zero-norm snapshot with normalize=True)")
+
+
+# ---- Gram matrices wider than the device eigensolver takes (rt_sym_eig_blocked, csrc/symeig_blocked.hip) --------------------
+BLOCK_MAX = 2048        # the device eigensolver's limit: the widest diagonal block
+MAX_BLOCKS = 8          # 16384 = 8 x 2048
+
+
+def block_partition(n, block_max=BLOCK_MAX):
+    """Widths of the p = ceil(n / block_max) contiguous column blocks of the block Rayleigh-Ritz route: they differ by
+    at most one, the wider ones first.  The rule of rt_sym_eig_blocked_plan_info, which refuses the same arguments."""
+    n, block_max = int(n), int(block_max)
+    if n < 1 or block_max < 1:
+        raise ValueError("block_partition: n and block_max must be positive")
+    p = -(-n // block_max)
+    if p > MAX_BLOCKS:
+        raise ValueError(f"block_partition: {p} blocks of at most {block_max} columns (more than {MAX_BLOCKS})")
+    return np.array([n // p + (1 if b < n % p else 0) for b in range(p)], dtype=np.int64)
+
+
+def blocked_floor(n) -> float:
+    """``floor_rel`` of the block Rayleigh-Ritz route: a block keeps the eigenvectors above floor_rel * lam_max.  n eps:
+    with it p tau^2 <= p n eps lam_1, the level to which any Gram eigensolve resolves an eigenvalue anyway."""
+    return float(int(n) * np.finfo(float).eps)
