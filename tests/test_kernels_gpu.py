@@ -6,6 +6,7 @@ from scipy.sparse import csr_matrix
 
 from oracle import romtime_oracle as oracle
 from tests.solve_cases import EPS, F_BATCHED, error_ratios, reference_solve, synthetic_hrom_terms
+from tests.sweep_cases import pattern_matrix, penta as _penta
 
 pytestmark = pytest.mark.gpu
 
@@ -259,19 +260,6 @@ def test_greedy_more_workgroups_than_the_chip_holds(ops):
     torch.cuda.synchronize()
 
 
-def _penta(N, rng):
-    offs = [-2, -1, 0, 1, 2]
-    rows, cols = [], []
-    for o in offs:
-        i = np.arange(max(0, -o), min(N, N - o))
-        rows.append(i)
-        cols.append(i + o)
-    rows, cols = np.concatenate(rows), np.concatenate(cols)
-    A = csr_matrix((rng.standard_normal(rows.size), (rows, cols)), shape=(N, N))
-    A.sort_indices()
-    return A
-
-
 @pytest.mark.parametrize("N,r", [(300, 8), (5000, 80), (2048, 33), (40000, 128), (1234, 1), (3000, 140)])
 def test_project_csr(ops, N, r):
     rng = np.random.RandomState(N)
@@ -294,31 +282,7 @@ def test_project_fused_pattern_variants(ops, pattern, r):
     not a multiple of 16, value vectors in both memory orders.  Against scipy's product (utils.py:96-113)."""
     rng = np.random.RandomState(len(pattern) * 100 + r)
     N = 1000 + 13
-    if pattern == "ragged_band":
-        A = _penta(N, rng).tolil()
-        drop = rng.rand(N) < 0.3
-        for i in np.nonzero(drop)[0]:
-            if 2 <= i < N - 2:
-                A[i, i - 2] = 0.0
-                A[i, i + 1] = 0.0
-        A = csr_matrix(A)
-    elif pattern == "wide":
-        rows = np.repeat(np.arange(N), 6)
-        cols = rng.randint(0, N, size=rows.size)
-        A = csr_matrix((rng.standard_normal(rows.size), (rows, cols)), shape=(N, N))
-    elif pattern == "mixed":
-        A = _penta(N, rng).tolil()
-        for i in rng.choice(N, size=12, replace=False):
-            A[i, (i + N // 2) % N] = 1.5
-        A = csr_matrix(A)
-    else:
-        A = _penta(N, rng).tolil()
-        for i in (0, 5, 6, 7, 500, N - 1):
-            A[i, :] = 0.0
-        A = csr_matrix(A)
-    A.eliminate_zeros()
-    A.sum_duplicates()
-    A.sort_indices()
+    A = pattern_matrix(pattern, N, rng)
     V, _ = np.linalg.qr(rng.standard_normal((N, r)))
     ip, ix = ops.to_device_index(A.indptr), ops.to_device_index(A.indices)
     Vd = ops.to_device(V)

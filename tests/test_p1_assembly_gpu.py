@@ -187,3 +187,96 @@ def test_ale_convection_of_the_moving_heat_problem_on_the_device():
             got = C[it * len(mus) + j]
             # the Dirichlet rows of a matrix kind are identity rows on both sides (coef does not touch them)
             np.testing.assert_allclose(got, ref, rtol=1e-12, atol=1e-14 * np.abs(ref).max())
+
+
+# ---- more states than one launch holds ----------------------------------------------------------------------------------
+def _closed_form_longdouble(kind, nx, rows, cols, h, coef, nodal):
+    """The closed forms stated at the top of p1_assembly.hip in np.longdouble: (n_states, m).  ``nodal``: (n_states,
+    nx + 1) nodal values (2 nx + 1 vertex / midpoint values for load_p2), or None for the kinds without a function."""
+    LD = np.longdouble
+    h, c = h.astype(LD)[:, None], coef.astype(LD)[:, None]
+    i, j = rows[None, :], (rows if cols is None else cols)[None, :]
+    d = j - i
+    inner = (i != 0) & (i != nx)
+    ic = np.clip(rows, 1, nx - 1)                                         # a valid node for the Dirichlet rows too
+    if kind == "load":
+        w = nodal.astype(LD)
+        return np.where(inner, c * h / 6 * (w[:, ic - 1] + 4 * w[:, ic] + w[:, ic + 1]), LD(0))
+    if kind == "load_p2":
+        w = nodal.astype(LD)
+        return np.where(inner, c * h / 3 * (w[:, 2 * ic - 1] + w[:, 2 * ic] + w[:, 2 * ic + 1]), LD(0))
+    if kind == "mass":
+        v = c * h * np.where(d == 0, LD(4) / 6, LD(1) / 6)
+    elif kind == "stiffness":
+        v = c / h * np.where(d == 0, LD(2), LD(-1))
+    elif kind == "convection":
+        v = c * np.where(d == 0, LD(0), np.where(d == 1, LD(-0.5), LD(0.5)))
+    else:
+        w = nodal.astype(LD)
+        b_prev, a_here = (w[:, ic - 1] + 2 * w[:, ic]) / 6, (2 * w[:, ic] + w[:, ic + 1]) / 6
+        v = c * np.where(d == -1, -b_prev, np.where(d == 0, b_prev - a_here, a_here))
+    v = np.where(np.abs(d) <= 1, v, LD(0))
+    return np.where(inner, v, np.where(d == 0, LD(1), LD(0)))
+
+
+@pytest.mark.parametrize("with_coef", [False, True])
+@pytest.mark.parametrize("kind,mode", [("mass", "none"), ("stiffness", "none"), ("convection", "none"), ("trilinear", "state"),
+                                       ("trilinear", "ramp"), ("load", "state"), ("load", "ramp"), ("load_p2", "state"),
+                                       ("load_p2", "poly")])
+def test_more_states_than_one_launch_holds(kind, mode, with_coef):
+    """rt_p1_local_assembly cuts n_states into slabs of 65535 along grid.y with per-slab offsets of h, coef, state and
+    out: 65537 states make a second slab of two.  Every entry of the 5 x 5 matrix (nx = 4) for every kind, every state
+    mode the kind allows, with and without coef, against the long-double closed forms within 4 ulp of their value
+    (two or three roundings per entry), in a guarded output.  The data keep what is not under test exact: the nodal
+    functions of the trilinear kind are multiples of 6 (its diagonal is a difference of two sixths), those of the load
+    kinds are positive (a sum of three terms without cancellation)."""
+    import ctypes as C
+
+    import torch
+
+    from romtime_amd import ops
+    from romtime_amd._lib import Context
+    from tests import guarded as gd
+
+    ctx = Context.current()
+    n_states, nx = 65537, 4
+    rng = np.random.RandomState(len(kind) * 10 + len(mode) + int(with_coef))
+    vector = kind in ("load", "load_p2")
+    rows, cols = (np.arange(nx + 1), None) if vector else [a.reshape(-1) for a in np.divmod(np.arange(25), 5)]
+    h = rng.uniform(0.1, 0.4, n_states)
+    coef = rng.uniform(0.5, 2.0, n_states) * rng.choice([-1.0, 1.0], n_states) if with_coef else None
+    width = 2 * nx + 1 if kind == "load_p2" else nx + 1
+    state, nodal, code = None, None, 0
+    if mode == "state":
+        nodal = 6.0 * rng.randint(-50, 51, (n_states, width)) if kind == "trilinear" else rng.uniform(0.5, 2.0, (n_states, width))
+        state, code = nodal, 1
+    elif mode == "ramp":
+        state = 24.0 * rng.randint(1, 40, n_states) if kind == "trilinear" else rng.uniform(0.5, 2.0, n_states)
+        nodal, code = state[:, None] * (np.arange(nx + 1) / nx)[None, :], 2      # amp * (node / nx): one rounding in float64
+    elif mode == "poly":
+        state, code = rng.uniform(0.5, 2.0, (n_states, 3)), 3
+        x = (0.5 * h[:, None]) * np.arange(width)[None, :]                        # x = 0.5 h k as the device forms it
+        a = state.astype(np.longdouble)
+        nodal = a[:, :1] + a[:, 1:2] * x + a[:, 2:3] * x.astype(np.longdouble) ** 2
+    ref = _closed_form_longdouble(kind, nx, rows, cols, h, np.ones(n_states) if coef is None else coef, nodal)
+    m = rows.size
+    out = gd.guarded_output((n_states, m))
+    operands = [(gd.guarded_operand(a.reshape(n_states, -1)), a.reshape(n_states, -1)) for a in (h, coef, state) if a is not None]
+    dev = iter(v for v, _ in operands)
+    hd, cd, sd = next(dev), (next(dev) if coef is not None else None), (next(dev) if state is not None else None)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(None)
+    rd, cld = ops.to_device_index(rows), (None if cols is None else ops.to_device_index(cols))
+    ctx.check(ctx.lib.rt_p1_local_assembly(ctx.handle, ops.P1_KINDS[kind], nx, ptr(rd), ptr(cld), m, n_states, ptr(hd), ptr(cd),
+                                           code, ptr(sd), ptr(out.t)), "rt_p1_local_assembly")
+    torch.cuda.synchronize()
+    got = out.t.cpu().numpy()
+    ref64 = ref.astype(np.float64)
+    err = np.abs(got.astype(np.longdouble) - ref)
+    bad = np.argwhere(err > 4 * np.spacing(np.abs(ref64)))
+    assert bad.size == 0, (bad[:4].tolist(), float((err / np.spacing(np.abs(ref64))).max()))
+    varies = with_coef or kind != "convection"                # convection without coef is the same table for every state
+    for s in (65534, 65535, 65536) if varies else ():         # the end of the first slab and the whole second one
+        assert not np.array_equal(ref64[s], ref64[s - 1]) and not np.array_equal(ref64[s], ref64[s - 65534])
+    assert out.check() == [], out.check()
+    for view, host in operands:
+        assert gd.operand_intact(view, host) == [], gd.operand_intact(view, host)
