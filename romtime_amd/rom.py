@@ -52,6 +52,11 @@ class RomConstructor(Reductor):
     # (``romtime_amd.fom``, rt_p1_fom_bdf_sweep) for a FOM that describes itself through ``p1_fom_recipe``; its snapshots
     # differ from the host loop's by rounding, so the caller chooses.
     SNAPSHOTS_ON = "host"
+    # Where ``solve`` / ``solve_many`` run.  "host": the reference's loop, one FOM callback per operator and step.
+    # "device": the whole BDF loop of all points in one sweep (``romtime_amd.online``, rt_hrom_bdf_sweep) for a model whose
+    # operators are all hyper-reduced or whose FOM is affine (``online.plan``); its trajectories differ from the host
+    # loop's by rounding, so the caller chooses.
+    ONLINE_ON = "host"
 
     def __init__(self, fom, grid, name=None) -> None:
         super().__init__(grid=grid)
@@ -126,6 +131,7 @@ class RomConstructor(Reductor):
         truncated = self.__class__(fom=self.fom, grid=self.grid, name=self.name)
         truncated.REDUCED_SOLVER = self.REDUCED_SOLVER
         truncated.GMRES_OPTIONS = deepcopy(self.GMRES_OPTIONS)
+        truncated.ONLINE_ON = self.ONLINE_ON
         truncated.setup(rnd=self.random_state)
         N = self.N
         assert n < N, "You want to remove too many modes from S-ROM to create ROM."
@@ -299,8 +305,25 @@ class RomConstructor(Reductor):
         ue = fenics.Expression(fom.exact_solution, degree=1, t=t, **mu)
         return function_to_array(fom.interpolate_func(ue, fom.V, mu, t)).copy()
 
+    def _online_on_device(self):
+        if self.ONLINE_ON not in ("host", "device"):
+            raise ValueError(f"ONLINE_ON must be 'host' or 'device', not {self.ONLINE_ON!r}")
+        return self.ONLINE_ON == "device"
+
+    def solve_many(self, mus, step=Stage.ONLINE, chunk=None):
+        """``solve`` for every point of ``mus``: with ONLINE_ON = "device" one sweep per chunk of at most ``chunk`` points
+        (None: all), otherwise the loop over ``solve``.  Returns ``online.OnlineSolutions``: ``idx``, ``mus``, ``ts``,
+        ``uN`` (n_mu, nt, r) on the device and ``storage(j)``; ``self.solutions`` is the last point's storage."""
+        from . import online
+
+        return online.solve_many(self, mus, step=step, chunk=chunk)
+
     def solve(self, mu, step):
         """BDF1/BDF2 time loop in the reduced space; zero initial condition (rom.py:430-555)."""
+        if self._online_on_device():
+            from . import online
+
+            return online.solve(self, mu, step)
         idx_mu, mu = self.add_mu(mu=mu, step=step)
         fom = self.fom
         track_error = fom.exact_solution is not None

@@ -77,6 +77,23 @@ def rom_bdf_sweep(V, indptr, indices, mass, terms, term_coef, tril, rhs_terms, r
     return out
 
 
+def fold_term(PT_U, basis_rom) -> torch.Tensor:
+    """The rows the local entries of a term multiply, ``Z^T = PT_U^-T basis_rom^T`` (m x r^2, or m x r for a vector
+    term), on the device.  An identity ``PT_U`` (the terms of an affine model, ``online.hrom_terms_from_affine``) needs
+    no solve; more than 128 entries are beyond the LDS-resident factorisation (include/romtime_hip.h) and go through
+    host LAPACK.  A zero pivot raises what ``np.linalg.solve`` raises (deim.py:491-492)."""
+    PT_U, basis_rom = np.asarray(PT_U, dtype=np.float64), np.asarray(basis_rom, dtype=np.float64)
+    m = PT_U.shape[0]
+    if np.array_equal(PT_U, np.eye(m)):
+        return ops.to_device(np.ascontiguousarray(basis_rom.T))
+    if m > 128:
+        return ops.to_device(np.linalg.solve(PT_U.T, basis_rom.T))
+    Zt, info = ops.dense_solve_multi(ops.to_device(np.ascontiguousarray(PT_U.T)), ops.to_device(np.ascontiguousarray(basis_rom.T)))
+    if int(info.item()) != 0:
+        raise np.linalg.LinAlgError("Singular matrix")
+    return Zt
+
+
 def hrom_bdf_sweep(mass, lin, nl, rhs, dt, bdf2=True, solver="direct", gmres_options=None):
     """Hyper-reduced online sweep on the device (``rt_hrom_bdf_sweep``): the time loop of
     ``RomConstructor*.solve`` with every reduced operator obtained by (M)DEIM interpolation,
@@ -95,13 +112,8 @@ def hrom_bdf_sweep(mass, lin, nl, rhs, dt, bdf2=True, solver="direct", gmres_opt
     ctx = Context.current()
 
     def fold(term):  # rows = the r x r (or r) arrays multiplied by each local entry: PT_U^T Z = basis_rom^T
-        PT_U, basis_rom = np.asarray(term["PT_U"], dtype=np.float64), np.asarray(term["basis_rom"], dtype=np.float64)
-        if PT_U.shape[0] > 128:   # beyond the LDS-resident factorisation (include/romtime_hip.h): host LAPACK
-            return np.linalg.solve(PT_U.T, basis_rom.T)
-        Zt, info = ops.dense_solve_multi(ops.to_device(np.ascontiguousarray(PT_U.T)), ops.to_device(np.ascontiguousarray(basis_rom.T)))
-        if int(info.item()) != 0:
-            raise np.linalg.LinAlgError("Singular matrix")           # what np.linalg.solve raises (deim.py:491-492)
-        return Zt.cpu().numpy()
+        Zt = term.get("Zt")   # folded already (``online.fold`` keeps them on the device from sweep to sweep)
+        return fold_term(term["PT_U"], term["basis_rom"]) if Zt is None else Zt
 
     blocks = [fold(mass)] + [fold(t) for t in lin] + ([fold(nl)] if nl is not None else [])
     rr = blocks[0].shape[1]
@@ -119,10 +131,10 @@ def hrom_bdf_sweep(mass, lin, nl, rhs, dt, bdf2=True, solver="direct", gmres_opt
     nt, n_mu, m_mass = tuple(mass["F"].shape)
     m_lin = sum(int(t["F"].shape[2]) for t in lin)
     m_nl = 0 if nl is None else int(nl["W"].shape[0])
-    Z = dev(np.vstack(blocks))
+    Z = blocks[0].contiguous() if len(blocks) == 1 else torch.cat(blocks, dim=0).contiguous()
     Fm = dev(mass["F"])
     Fl = cat(lin) if lin else None
-    Zf = dev(np.vstack([fold(t) for t in rhs])) if rhs else None
+    Zf = torch.cat([fold(t) for t in rhs], dim=0).contiguous() if rhs else None
     Ff = cat(rhs) if rhs else None
     m_rhs = 0 if Zf is None else Zf.shape[0]
     W = dev(nl["W"]) if nl is not None else None
