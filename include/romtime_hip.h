@@ -204,6 +204,17 @@ int rt_project_csr_batched(rt_ctx* ctx, const int64_t* indptr, const int64_t* in
                            const double* data_batch, int64_t ld_data, int data_layout, int64_t B, int64_t N,
                            const double* V, int64_t ldv, int64_t r, double* AN_batch);
 
+/* How the fused projection (r <= 128) walks a CSR pattern of N rows (indptr, indices: DEVICE arrays): it takes the rows
+ * in stages of 32 and reads one record per stage from a table built on the device.  This builds that table with the
+ * kernel the projection uses, copies it back and unpacks it - tests and diagnostics; read-only, it launches nothing
+ * else and synchronises the ctx's stream.  records: HOST array [ceil(N / 32)][6] = {e0 first entry of the stage's rows,
+ * lo first row of their column window, ne entries, nrow rows of the window (0: the stage is not windowed, its rows are
+ * gathered from global memory, and lo is the stage's first row), mr longest row, uni 1 when all 32 rows have mr entries}.
+ * A stage is windowed when its columns and its own rows span at most 48 rows and it has at most 512 entries.
+ * *any_unwindowed (HOST) = 1 when some stage is not. */
+int rt_project_stage_info(rt_ctx* ctx, const int64_t* indptr, const int64_t* indices, int64_t N, int64_t* records,
+                          int* any_unwindowed);
+
 /* ---- reduced solve (np.linalg.solve: deim.py:491-492; gmres on a dense r x r: rom.py:492) --- */
 
 /* Solve K_b x_b = rhs_b for b < B by LU with partial pivoting, one workgroup per system.

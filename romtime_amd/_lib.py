@@ -65,6 +65,7 @@ SIGNATURES = {
     "rt_csr_spmm": (_int, [_p, _p, _p, _p, _i64, _p, _i64, _i64, _p, _i64]),
     "rt_project_csr": (_int, [_p, _p, _p, _p, _i64, _p, _i64, _i64, _p]),
     "rt_project_csr_batched": (_int, [_p, _p, _p, _p, _i64, _int, _i64, _i64, _p, _i64, _i64, _p]),
+    "rt_project_stage_info": (_int, [_p, _p, _p, _i64, C.POINTER(_i64), C.POINTER(_int)]),
     "rt_dense_solve_batched": (_int, [_p, _p, _p, _i64, _i64, _p]),
     "rt_dense_solve_multi": (_int, [_p, _p, _i64, _p, _p, _i64, _p]),
     "rt_tracked_solve_batched": (_int, [_p, _p, _p, _p, _i64, _i64, _int, _p]),

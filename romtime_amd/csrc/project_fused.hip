@@ -25,7 +25,9 @@
 
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
+#include <vector>
 
 // Timing-only builds (ROMTIME_EXTRA_HIPFLAGS=-DROMTIME_PF_ABLATE python -m romtime_amd.build, then ROMTIME_PF_FLAGS =
 // 8: no buffer-descriptor fetch, 16: no gather, 32: no MFMAs, 64: no global loads, 16384: time stamps around the
@@ -511,6 +513,36 @@ int rt_project_stage_table(rt_ctx* ctx, const int64_t* indptr, const int64_t* in
                      reinterpret_cast<const long*>(indptr), reinterpret_cast<const long*>(indices), (long)N,
                      reinterpret_cast<StageRec*>(static_cast<char*>(table) + TABLE_HEADER), static_cast<int*>(table));
   RT_HIP_CHECK(ctx, hipGetLastError());
+  return RT_OK;
+}
+
+// The table of rt_project_stage_table for this pattern, read back and unpacked (tests and diagnostics): the same kernel
+// and the same bytes the projection reads.  Nothing else is launched.
+extern "C" int rt_project_stage_info(rt_ctx* ctx, const int64_t* indptr, const int64_t* indices, int64_t N, int64_t* records,
+                                     int* any_unwindowed) {
+  if (!ctx) return RT_ERR_ARG;
+  RT_ARG_CHECK(ctx, indptr && indices && records && any_unwindowed && N >= 1 && N < (1LL << 31) - 2 * PK);
+  const size_t stages = (size_t)((N + PK - 1) / PK), bytes = rt_project_stage_table_bytes(N);
+  void* table = nullptr;
+  RT_TRY(rt_scratch(ctx, bytes, &table));
+  RT_TRY(rt_project_stage_table(ctx, indptr, indices, N, table));
+  std::vector<char> host(bytes);
+  RT_HIP_CHECK(ctx, hipMemcpyAsync(host.data(), table, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  RT_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  int any = 0;
+  memcpy(&any, host.data(), sizeof(int));
+  *any_unwindowed = any != 0 ? 1 : 0;
+  for (size_t s = 0; s < stages; ++s) {
+    StageRec rc;
+    memcpy(&rc, host.data() + TABLE_HEADER + s * sizeof(StageRec), sizeof(StageRec));
+    int64_t* o = records + 6 * s;
+    o[0] = rc.e0;
+    o[1] = rc.lo;
+    o[2] = rec_ne(rc.packed);
+    o[3] = rec_nrow(rc.packed);
+    o[4] = rec_mr(rc.packed);
+    o[5] = rec_uni(rc.packed) ? 1 : 0;
+  }
   return RT_OK;
 }
 

@@ -360,6 +360,20 @@ def project_csr_batched(indptr, indices, data_batch: torch.Tensor, V: torch.Tens
     return AN
 
 
+def project_stage_info(indptr, indices):
+    """The stage table the fused projection reads for this pattern (device index tensors), read back:
+    (records, any_unwindowed) with records an int64 array [stages][6] = (e0, lo, ne, nrow, mr, uni) per stage of 32 rows;
+    nrow = 0 marks a stage that is not windowed.  rt_project_stage_info; synchronises the stream."""
+    ctx = Context.current()
+    N = indptr.numel() - 1
+    records = np.zeros(((N + 31) // 32, 6), dtype=np.int64)
+    any_unwindowed = C.c_int(0)
+    ctx.check(ctx.lib.rt_project_stage_info(ctx.handle, _ptr(indptr), _ptr(indices), N,
+                                            records.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(any_unwindowed)),
+              "rt_project_stage_info")
+    return records, bool(any_unwindowed.value)
+
+
 def dense_solve(K: torch.Tensor, b: torch.Tensor):
     """Solve K x = b (K: [r,r] or [B,r,r]; b: [r] or [B,r]). Returns (x, info). Inputs are not modified."""
     ctx = Context.current()

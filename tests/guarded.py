@@ -8,6 +8,8 @@ output, and integer-valued data whose products a correct kernel reproduces bit f
   finds, bitwise, every word written outside the view and every word of the view left unwritten.
 * ``exact_operands`` draws integers scaled by powers of two whose products and partial sums are all exact in float64:
   the NumPy product is then the exact answer, independent of summation order.
+* ``project_guarded`` runs the reduced projection on such operands and such an output and asserts all of the above
+  (tests/test_guarded_kernels_gpu.py, tests/test_project_truth_gpu.py).
 * ``gemm_plan`` and friends restate the dispatch rules of the HIP library in Python, so that a test can assert the
   route its case takes (``Context.launch_info``): a changed threshold fails loudly instead of dropping coverage.
 
@@ -209,6 +211,49 @@ def mismatch(got, want) -> str:
         return f"shape {got.shape} vs {want.shape}"
     i = tuple(bad[0])
     return f"{len(bad)} entries differ, first at {i}: {got[i]!r} vs {want[i]!r}"
+
+
+# ---- the reduced projection on guarded buffers ---------------------------------------------------------------------------
+
+def device_pattern(indptr, indices, device="cuda"):
+    """(indptr, indices) of a CSR pattern as device tensors; indices keeps one word when the pattern has no entry, so
+    that its pointer is not null."""
+    ip = torch.from_numpy(np.ascontiguousarray(indptr, dtype=np.int64)).to(device)
+    ix = torch.zeros(max(len(indices), 1), dtype=torch.int64, device=device)
+    ix[:len(indices)] = torch.from_numpy(np.ascontiguousarray(indices, dtype=np.int64))
+    return ip, ix
+
+
+def project_guarded(ctx, pattern, data, V, dlay="C", dpad=0, vpad=0, vmis=False, vguard=GUARD, single=False):
+    """A_N[b] = V^T (A_b V) through rt_project_csr_batched (rt_project_csr with ``single``: one value vector) with V
+    (N x r) and data (nnz x B) as guarded operands and the result in a guarded output.  ``pattern``: (indptr, indices),
+    NumPy or ``device_pattern`` tensors.  Requires every output word written, nothing written outside the output, and
+    operands and their poison intact; returns (A_N as a (B, r, r) host array, launch_info, the guarded V)."""
+    import ctypes as C
+
+    # where the view starts inside its buffer: data_ptr() of a view without elements (nnz = 0) is null
+    P = lambda t: C.c_void_p(t.untyped_storage().data_ptr() + t.element_size() * t.storage_offset())
+    ip, ix = pattern if isinstance(pattern[0], torch.Tensor) else device_pattern(*pattern)
+    (N, r), (nnz, B) = V.shape, data.shape
+    assert ip.numel() == N + 1
+    Vd = guarded_operand(V, "C", vpad, vmis, guard=vguard)
+    Dd = guarded_operand(data, dlay, dpad, False)
+    ldd, dl = leading_dim(Dd)
+    AN = guarded_output((B * r, r))
+    if single:
+        assert B == 1 and dl == "F"
+        ctx.check(ctx.lib.rt_project_csr(ctx.handle, P(ip), P(ix), P(Dd), N, P(Vd), r + vpad, r, P(AN.t)), "rt_project_csr")
+    else:
+        ctx.check(ctx.lib.rt_project_csr_batched(ctx.handle, P(ip), P(ix), P(Dd), ldd, {"C": 0, "F": 1}[dl], B, N, P(Vd), r + vpad,
+                                                 r, P(AN.t)), "rt_project_csr_batched")
+    info = ctx.launch_info()
+    torch.cuda.synchronize()
+    got = AN.t.cpu().numpy().reshape(B, r, r)
+    assert AN.check() == [], AN.check()
+    for view, host in ((Vd, V), (Dd, data)):
+        problems = operand_intact(view, host)
+        assert problems == [], problems
+    return got, info, Vd
 
 
 # ---- the dispatch rules of the HIP library, restated (route assertions) -----------------------------------------------

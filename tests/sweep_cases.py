@@ -436,6 +436,8 @@ for _r, _N in ((1, 100), (16, 200), (17, 200), (80, 300), (81, 300), (128, 300))
 D_CASES.update(square_r16=dict(N=16, r=16), N_257=dict(N=257, r=16), N_3_r1=dict(N=3, r=1),
                points_1=dict(N=100, r=8, n_mu=1), points_33=dict(N=100, r=8, n_mu=33),
                horizon_1=dict(N=100, r=8, nt=1), horizon_2=dict(N=100, r=8, nt=2))
+for _r in (64, 112):     # the tile layouts of 4 and 7 block rows, with the sweep's own stage table and its banded hint
+    D_CASES[f"size_r{_r}"] = dict(N=300, r=_r, n_mu=2)
 D_GMRES_CASES = dict(wide_r7=dict(N=413, r=7, pattern="wide"), tril_none=dict(N=150, r=5, tril=False))
 D_ZERO_CASES = dict(rhs_none=dict(N=150, r=5, n_rhs=0))
 

@@ -26,6 +26,20 @@ def test_binding_table_matches_header():
     assert set(_lib.SIGNATURES) == _declared()
 
 
+def test_stage_table_query_is_declared_exported_and_bound():
+    """rt_project_stage_info, the read-only query the projection truth tests stand on: in the header, in the library and
+    in the binding table with the header's argument list (ctx, indptr, indices, N, records, any_unwindowed)."""
+    import ctypes as C
+
+    assert "rt_project_stage_info" in _declared()
+    fn = _lib.load().rt_project_stage_info
+    assert fn.restype is C.c_int
+    assert fn.argtypes == [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+    # a null ctx is refused before anything is touched (no GPU needed)
+    rec, flag = (C.c_int64 * 6)(), C.c_int(7)
+    assert fn(None, None, None, 1, rec, C.byref(flag)) < 0 and flag.value == 7 and list(rec) == [0] * 6
+
+
 def test_header_cites_reference_for_each_hot_entry_point():
     text = open(os.path.join(REPO, "include", "romtime_hip.h")).read()
     for needle in ("pod.py", "deim.py:517-561", "utils.py:96-113", "mdeim.py:153-192", "rom.py"):

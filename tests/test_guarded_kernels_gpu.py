@@ -340,25 +340,17 @@ def _project_case(ctx, cus, N, r, B, dlay, dpad, vpad, vmis, route, extra=2, vgu
     assert nnz * 2.0 ** (2 * bv + 10) < 2.0 ** 53
     data = exact_operands(rng, (nnz, B), 10)
     V = exact_operands(rng, (N, r), bv, gd.graded_exponents(rng, r, 60))
-    Vd = guarded_operand(V, "C", vpad, vmis, guard=vguard)
-    Dd = guarded_operand(data, dlay, dpad, False)
-    ldd, dl = gd.leading_dim(Dd)
-    AN = guarded_output((B * r, r))
-    ip, ix = torch.from_numpy(indptr).cuda(), torch.from_numpy(indices).cuda()
-    ctx.check(ctx.lib.rt_project_csr_batched(ctx.handle, P(ip), P(ix), P(Dd), ldd, LAY[dl], B, N, P(Vd), r + vpad, r, P(AN.t)),
-              "rt_project_csr_batched")
-    info = ctx.launch_info()
+    # guarded operands and output; written, bounded and intact are asserted in there (tests/guarded.py)
+    got, info, Vd = gd.project_guarded(ctx, (indptr, indices), data, V, dlay, dpad, vpad, vmis, vguard)
     if route == "fused":
         rp = 16 * (-(-r // 16))
         assert info["tile"] == (rp, rp) and info["grid"] == B * info["splits"], info
     else:
         chunk = max(min(B, (2 << 30) // (8 * N * r)), 1)
         assert info == gd.gemm_plan(r, (r if chunk == 1 else chunk * r), N, False, True, cus), info
-    got = _host(AN.t).reshape(B, r, r)
     for b in range(B):
         A = sp.csr_matrix((data[:, b], indices, indptr), shape=(N, N))
         _exact(got[b], V.T @ (A @ V))
-    _clean([AN], [(Vd, V), (Dd, data)])
     return Vd
 
 
