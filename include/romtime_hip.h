@@ -453,6 +453,32 @@ int rt_p1_fom_bdf_sweep(rt_ctx* ctx, const rt_fom_desc* desc, double* U_out, int
  * followed (U_out and info, which it does not take, count as given): the same return code, and on RT_OK info3 (may be
  * NULL) = {workgroups, partitions per system, rows per partition}. */
 int rt_p1_fom_bdf_sweep_plan_info(int num_cus, const rt_fom_desc* desc, int64_t ld_step, int64_t stride_mu, int64_t* info3);
+/* The same sweep, certified by the backward error of every step's solve instead of by diagonal dominance, since version
+ * 410.  Dominance, |d| >= |l| + |u|, holds for the rows above only where about |w| dt/h <= 2 bdf/3 + 2 alpha dt/h^2 - a
+ * CFL number below one or a cell Peclet number below two - and is sufficient, not necessary: the unpivoted elimination
+ * is backward stable far outside that regime (the piston at alpha = 1e-6, CFL 10 to 2000), and this entry measures it.
+ *   - The solve is that of rt_p1_fom_bdf_sweep: for equal inputs U_out has the same bits.
+ *   - defect: n_mu x desc->nt DEVICE doubles, defect[j nt + s] = the componentwise backward error of step s of point j,
+ *       omega = max over the interior rows i of |rhs_i - (l_i x_{i-1} + d_i x_i + u_i x_{i+1})|
+ *                                               / (|l_i x_{i-1}| + |d_i x_i| + |u_i x_{i+1}| + |rhs_i|)      (0/0 = 0),
+ *     x the new state, the rows formed again by the formulas above from the same two older states, l_1 = u_{nx-1} = 0:
+ *     the smallest relative perturbation of every entry of the step's system for which x solves it exactly.  +inf where
+ *     a pivot, a partition's last unknown or a value of the new state is not finite.
+ *   - info: n_mu DEVICE ints, each 0, or 1 + the global index of the first step whose defect is not finite or above
+ *     defect_tol.  Dominance is not looked at.  The sweep of a flagged point carries on; a flag never affects another point.
+ *   - The argument checks of rt_p1_fom_bdf_sweep; a null defect and a defect_tol that is negative or NaN return
+ *     RT_ERR_ARG before any launch.  The new state goes to a third state array, so that both older states are still
+ *     there when the defect is formed: 48 KiB x ceil((nx-1)/1024) per point of ctx leaf arena (six arrays, not five),
+ *     RT_ERR_UNSUPPORTED beyond 64 GiB; the defect pass reads three arrays more per step (thirteen, not ten).
+ *   - Everything else as rt_p1_fom_bdf_sweep: one workgroup per point, no waiting between workgroups, no floating-point
+ *     atomics, nx <= 2^22; the bits of a trajectory AND its defects do not depend on n_mu, the point's place in the batch
+ *     or how the horizon is cut into calls.  No pivoting and no refinement: a flagged point is not to be trusted. */
+int rt_p1_fom_bdf_sweep_certified(rt_ctx* ctx, const rt_fom_desc* desc, double* U_out, int64_t ld_step, int64_t stride_mu,
+                                  double defect_tol, double* defect, int* info);
+/* The plan query of the certified entry: as rt_p1_fom_bdf_sweep_plan_info, info4 (may be NULL) = {workgroups, partitions
+ * per system, rows per partition, scratch bytes per point}. */
+int rt_p1_fom_bdf_sweep_certified_plan_info(int num_cus, const rt_fom_desc* desc, int64_t ld_step, int64_t stride_mu,
+                                            int64_t* info4);
 
 /* ---- small symmetric eigenproblem of the Gram matrix, on the device (3 <= n <= 2048) ---------- */
 /* Householder tridiagonalisation (32 cooperating workgroups, 128 for n > 512; matrix resident in LDS) + Sturm

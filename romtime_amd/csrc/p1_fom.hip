@@ -35,9 +35,21 @@
 // lane p reads and writes element p of a row, so every access of A and C is coalesced, and the neighbours across a
 // partition edge are lane p-1's last and lane p+1's first row.  Only U_out and u_init have the natural layout: they pass
 // through an LDS tile of 8 rows of every partition (64-byte runs in memory).
+//
+// The certified mode (rt_p1_fom_bdf_sweep_certified, the CERT instantiation) runs the same passes A, B and C - the same
+// bits in U_out - and does not look at dominance.  Pass C writes the new state to a third state array (six arrays per
+// point instead of five), so that u^n and u^n-1 are still there for
+//
+//   D  the rows once more (fom_row, the function pass A forms them with) against the new state: the componentwise
+//      backward error  omega = max_i |rhs_i - (l_i x_i-1 + d_i x_i + u_i x_i+1)| / (|l_i x_i-1| + |d_i x_i| + |u_i x_i+1| + |rhs_i|)
+//      of the step, reduced over the wave (wave_ops.h) and over the workgroup through LDS; a non-finite pivot, xB, state
+//      value, residual or denominator makes it +inf (fmax drops NaNs: "non-finite seen" is a flag of its own).
+//
+// D reads three arrays more per step (thirteen instead of ten).
 #include <cmath>
 
 #include "common.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -58,12 +70,50 @@ struct FomParams {
   double* U;
   int* info;
   double* arena;
+  double defect_tol;   // certified mode only
+  double* defect;
 };
 
 struct FomPlan {
   long m, parts;
-  size_t scratch;
+  size_t scratch, per_point;
 };
+
+// The scalars of one step's rows, and the rows themselves: stated once for pass A and for the defect pass D.
+struct FomStep {
+  double dt, ws, c0, c1n, h, mo, md, ah, h6, dth, a0, a1, a2, a2h;
+  bool two;
+};
+
+__device__ __forceinline__ FomStep fom_step(const double* tb, double dt, double inv_nx, double ws, bool two) {
+  FomStep S;
+  const double h = tb[0], alpha = tb[1], c1 = tb[3];
+  const double bdf = two ? 1.5 : 1.0;
+  S.dt = dt, S.ws = ws, S.two = two, S.h = h, S.c0 = tb[2], S.a0 = tb[4], S.a1 = tb[5], S.a2 = tb[6];
+  S.mo = bdf * h / 6.0, S.md = bdf * 4.0 * h / 6.0, S.ah = alpha / h, S.h6 = h / 6.0, S.dth = dt * h;
+  S.c1n = c1 * inv_nx, S.a2h = S.a2 * h * h / 6.0;
+  return S;
+}
+
+// w and past of a node from its two older values
+__device__ __forceinline__ double fom_w(const FomStep& S, double un, double vn, int node) {
+  return S.ws * (S.two ? 2.0 * un - vn : un) + S.c0 + S.c1n * (double)node;
+}
+
+__device__ __forceinline__ double fom_past(const FomStep& S, double un, double vn) { return S.two ? 2.0 * un - 0.5 * vn : un; }
+
+// row of node i from w and past of the nodes i-1, i, i+1; l_1 and u_nx-1 are NOT yet zeroed (dominance looks at them)
+__device__ __forceinline__ void fom_row(const FomStep& S, double wL, double wC, double wR, double pL, double pC, double pR, int i,
+                                        double& l, double& d, double& u, double& rhs) {
+  constexpr double sixth = 1.0 / 6.0;
+  const double bp = (wL + 2.0 * wC) * sixth, ai = (2.0 * wC + wR) * sixth;
+  l = S.mo + S.dt * (-S.ah - bp);
+  d = S.md + S.dt * (2.0 * S.ah + bp - ai);
+  u = S.mo + S.dt * (-S.ah + ai);
+  // h/3 (f(x - h/2) + f(x) + f(x + h/2)) = h (f(x) + a2 h^2 / 6) for the quadratic f
+  const double x = (double)i * S.h;
+  rhs = S.h6 * (pL + 4.0 * pC + pR) + S.dth * (fma(fma(S.a2, x, S.a1), x, S.a0) + S.a2h);
+}
 
 // rows k0 .. k0+KT-1 of every partition between the LDS tile and a state in its natural layout (node = 1 + p m + k)
 __device__ __forceinline__ void fom_tile_to_global(const double* tile, double* dst, int k0, int m, int n) {
@@ -85,6 +135,7 @@ __device__ __forceinline__ void fom_global_to_tile(double* tile, const double* s
 }
 
 // nx <= 2^22: node numbers and the offsets inside a point's arrays (m x 1024 <= 2^22 words) fit 32 bits
+template <bool CERT>
 __global__ __launch_bounds__(FOM_THREADS) void p1_fom_kernel(const FomParams P) {
   extern __shared__ double fom_lds[];
   double* tile = fom_lds;                               // FOM_THREADS x FOM_TILE_LD
@@ -98,9 +149,10 @@ __global__ __launch_bounds__(FOM_THREADS) void p1_fom_kernel(const FomParams P) 
   const int mp = n - r0 > m ? m : (n - r0 < 0 ? 0 : n - r0);   // rows of this partition (only the last active one may be short)
   const bool active = mp > 0;
   const bool last_part = active && (r0 + mp == n);
-  double* base = P.arena + (size_t)j * 5 * m * NT;
+  double* base = P.arena + (size_t)j * (CERT ? 6 : 5) * m * NT;
   double* S0 = base;                                    // u^n
-  double* S1 = base + (size_t)m * NT;                   // u^{n-1}; the new state is written over it
+  double* S1 = base + (size_t)m * NT;                   // u^{n-1}; the new state is written over it, or (CERT) to S2
+  double* S2 = CERT ? base + (size_t)5 * m * NT : nullptr;
   double* const fc = base + (size_t)2 * m * NT;
   double* const ff = base + (size_t)3 * m * NT;
   double* const fy = base + (size_t)4 * m * NT;
@@ -122,18 +174,16 @@ __global__ __launch_bounds__(FOM_THREADS) void p1_fom_kernel(const FomParams P) 
     __syncthreads();
   }
 
-  const double dt = P.dt, inv_nx = 1.0 / (double)P.nx, sixth = 1.0 / 6.0;
+  const double dt = P.dt, inv_nx = 1.0 / (double)P.nx;
   const double ws = P.state_in_w ? 1.0 : 0.0;
   int info = 0;
   for (long s = 0; s < P.nt; ++s) {
     const long g = P.first_step + s;
     const bool two = P.bdf2 && g > 0;
     const double* tb = P.tab + ((size_t)s * P.n_mu + j) * 7;
-    const double h = tb[0], alpha = tb[1], c0 = tb[2], c1 = tb[3], a0 = tb[4], a1 = tb[5], a2 = tb[6];
-    const double bdf = two ? 1.5 : 1.0;
-    const double mo = bdf * h / 6.0, md = bdf * 4.0 * h / 6.0, ah = alpha / h, h6 = h / 6.0, dth = dt * h;
-    const double c1n = c1 * inv_nx, a2h = a2 * h * h / 6.0;
-    bool bad = false;
+    const FomStep T = fom_step(tb, dt, inv_nx, ws, two);
+    double* const Sn = CERT ? S2 : S1;     // the new state
+    bool bad = false;                      // a row not dominant or a pivot not finite; CERT: a pivot or xB not finite
     double cl = 0.0, fl = 0.0, yl = 0.0;   // the partition's last row after A
     double Y = 0.0, G = 0.0, F = 0.0;      // its first unknown in terms of xB and xL
 
@@ -146,9 +196,8 @@ __global__ __launch_bounds__(FOM_THREADS) void p1_fom_kernel(const FomParams P) 
         if (two) vnL = S1[(m - 1) * NT + p - 1];
       }
       const double unC = S0[p], vnC = two ? S1[p] : 0.0;
-      double wL = ws * (two ? 2.0 * unL - vnL : unL) + c0 + c1n * (double)r0;
-      double wC = ws * (two ? 2.0 * unC - vnC : unC) + c0 + c1n * (double)(r0 + 1);
-      double pL = two ? 2.0 * unL - 0.5 * vnL : unL, pC = two ? 2.0 * unC - 0.5 * vnC : unC;
+      double wL = fom_w(T, unL, vnL, r0), wC = fom_w(T, unC, vnC, r0 + 1);
+      double pL = fom_past(T, unL, vnL), pC = fom_past(T, unC, vnC);
       double cprev = 0.0, fprev = -1.0, yprev = 0.0, pi = 1.0;
       for (int kb = 0; kb < mp; kb += FOM_KB) {
         // the right-hand neighbours of FOM_KB rows are asked for together: the elimination below is one dependent chain,
@@ -172,16 +221,10 @@ __global__ __launch_bounds__(FOM_THREADS) void p1_fom_kernel(const FomParams P) 
           if (k >= mp) break;
           const int i = r0 + k + 1;         // node of this row
           const double unR = ur[q], vnR = vr[q];
-          const double wR = ws * (two ? 2.0 * unR - vnR : unR) + c0 + c1n * (double)(i + 1);
-          const double pR = two ? 2.0 * unR - 0.5 * vnR : unR;
-          const double bp = (wL + 2.0 * wC) * sixth, ai = (2.0 * wC + wR) * sixth;
-          double l = mo + dt * (-ah - bp);
-          const double d = md + dt * (2.0 * ah + bp - ai);
-          double u = mo + dt * (-ah + ai);
-          // h/3 (f(x - h/2) + f(x) + f(x + h/2)) = h (f(x) + a2 h^2 / 6) for the quadratic f
-          const double x = (double)i * h;
-          const double rhs = h6 * (pL + 4.0 * pC + pR) + dth * (fma(fma(a2, x, a1), x, a0) + a2h);
-          bad |= fabs(d) < fabs(l) + fabs(u);
+          const double wR = fom_w(T, unR, vnR, i + 1), pR = fom_past(T, unR, vnR);
+          double l, d, u, rhs;
+          fom_row(T, wL, wC, wR, pL, pC, pR, i, l, d, u, rhs);
+          if constexpr (!CERT) bad |= fabs(d) < fabs(l) + fabs(u);
           if (i == 1) l = 0.0;              // u_0 = u_nx = 0
           if (i == n) u = 0.0;
           const double r = 1.0 / (d - l * cprev);
@@ -229,8 +272,10 @@ __global__ __launch_bounds__(FOM_THREADS) void p1_fom_kernel(const FomParams P) 
     }
     const double xB = D / B;
     bad |= active && !std::isfinite(1.0 / B);
+    if constexpr (CERT) bad |= active && !std::isfinite(xB);
     shb[p] = xB;
-    if (__syncthreads_or(bad) && info == 0) info = (int)(1 + g);
+    const bool any_bad = __syncthreads_or(bad);
+    if (!CERT && any_bad && info == 0) info = (int)(1 + g);
 
     // ---- C: upwards inside the partition, x_k = y_k - c_k x_k+1 - f_k xL from x_last = xB, tile by tile
     const double xL = p > 0 ? shb[p - 1] : 0.0;
@@ -254,7 +299,7 @@ __global__ __launch_bounds__(FOM_THREADS) void p1_fom_kernel(const FomParams P) 
         if (k < mp) {
           const double x = k + 1 == mp ? xB : yq[kk] - cq[kk] * xnext - fq[kk] * xL;
           xnext = x;
-          S1[k * NT + p] = x;
+          Sn[k * NT + p] = x;
           tile[p * FOM_TILE_LD + kk] = x;
         }
       }
@@ -266,16 +311,83 @@ __global__ __launch_bounds__(FOM_THREADS) void p1_fom_kernel(const FomParams P) 
       out[0] = 0.0;
       out[P.nx] = 0.0;
     }
-    double* t = S0;
-    S0 = S1;
-    S1 = t;
+
+    if constexpr (CERT) {
+      // ---- D: the rows again, from the same two older states, against the new state (every lane's rows of Sn are
+      // visible: the tiles of pass C end with a barrier).  xB (shb) is no longer read: the wave maxima go there.
+      double om = 0.0;
+      bool nf = false;
+      if (active) {
+        double unL = 0.0, vnL = 0.0, xl = 0.0;
+        if (p > 0) {
+          unL = S0[(m - 1) * NT + p - 1];
+          if (two) vnL = S1[(m - 1) * NT + p - 1];
+          xl = Sn[(m - 1) * NT + p - 1];
+        }
+        const double unC = S0[p], vnC = two ? S1[p] : 0.0;
+        double xc = Sn[p];
+        double wL = fom_w(T, unL, vnL, r0), wC = fom_w(T, unC, vnC, r0 + 1);
+        double pL = fom_past(T, unL, vnL), pC = fom_past(T, unC, vnC);
+        for (int kb = 0; kb < mp; kb += FOM_KB) {
+          double ur[FOM_KB], vr[FOM_KB], xr[FOM_KB];
+#pragma unroll
+          for (int q = 0; q < FOM_KB; ++q) {
+            const int k = kb + q;
+            ur[q] = vr[q] = xr[q] = 0.0;
+            if (k + 1 < mp) {
+              ur[q] = S0[(k + 1) * NT + p];
+              if (two) vr[q] = S1[(k + 1) * NT + p];
+              xr[q] = Sn[(k + 1) * NT + p];
+            } else if (k + 1 == mp && !last_part) {
+              ur[q] = S0[p + 1];
+              if (two) vr[q] = S1[p + 1];
+              xr[q] = Sn[p + 1];
+            }
+          }
+#pragma unroll
+          for (int q = 0; q < FOM_KB; ++q) {
+            const int k = kb + q;
+            if (k >= mp) break;
+            const int i = r0 + k + 1;
+            const double unR = ur[q], vnR = vr[q], xR = xr[q];
+            const double wR = fom_w(T, unR, vnR, i + 1), pR = fom_past(T, unR, vnR);
+            double l, d, u, rhs;
+            fom_row(T, wL, wC, wR, pL, pC, pR, i, l, d, u, rhs);
+            if (i == 1) l = 0.0;
+            if (i == n) u = 0.0;
+            const double res = fma(-u, xR, fma(-d, xc, fma(-l, xl, rhs)));
+            const double den = fabs(l * xl) + fabs(d * xc) + fabs(u * xR) + fabs(rhs);
+            nf |= !std::isfinite(xc) || !std::isfinite(res) || !std::isfinite(den);
+            // den == 0 (finite): every term is zero and so is the residual
+            om = fmax(om, den > 0.0 ? fabs(res) / den : 0.0);
+            wL = wC, wC = wR, pL = pC, pC = pR, xl = xc, xc = xR;
+          }
+        }
+      }
+      om = rtw::wave_max(om);
+      if ((p & 63) == 0) shb[p >> 6] = om;
+      const bool any_nf = __syncthreads_or(nf) || any_bad;
+      double omega = shb[0];
+      for (int q = 1; q < FOM_THREADS / 64; ++q) omega = fmax(omega, shb[q]);
+      if (any_nf) omega = INFINITY;
+      if (p == 0) P.defect[(size_t)j * P.nt + s] = omega;
+      if (omega > P.defect_tol && info == 0) info = (int)(1 + g);   // +inf is above every tolerance
+      double* t = S0;
+      S0 = S2;
+      S2 = S1;
+      S1 = t;
+    } else {
+      double* t = S0;
+      S0 = S1;
+      S1 = t;
+    }
   }
   if (p == 0) P.info[j] = info;
 }
 
 // Argument checks and the partitioning: host logic only, shared by the entry point and the plan query.
-int fom_plan(const rt_fom_desc* d, const double* U_out, int64_t ld_step, int64_t stride_mu, const int* info, FomPlan* plan,
-             const char** why) {
+int fom_plan(const rt_fom_desc* d, const double* U_out, int64_t ld_step, int64_t stride_mu, const int* info, bool certified,
+             FomPlan* plan, const char** why) {
 #define FOM_ARG(cond)                      \
   do {                                     \
     if (!(cond)) {                         \
@@ -300,40 +412,47 @@ int fom_plan(const rt_fom_desc* d, const double* U_out, int64_t ld_step, int64_t
   const long n = d->nx - 1;
   const long m = (n + FOM_THREADS - 1) / FOM_THREADS;
   const long parts = (n + m - 1) / m;
-  const size_t scratch = (size_t)d->n_mu * 5 * m * FOM_THREADS * 8;
+  const size_t per_point = (size_t)(certified ? 6 : 5) * m * FOM_THREADS * 8;   // the certified mode keeps a third state
+  const size_t scratch = (size_t)d->n_mu * per_point;
   if (scratch > FOM_MAX_SCRATCH) {
-    *why = "rt_p1_fom_bdf_sweep: more than 64 GiB of states and factors (40 KiB x ceil((nx-1)/1024) per point): sweep fewer points per call";
+    *why = certified ? "rt_p1_fom_bdf_sweep_certified: more than 64 GiB of states and factors (48 KiB x ceil((nx-1)/1024) per point): sweep fewer points per call"
+                     : "rt_p1_fom_bdf_sweep: more than 64 GiB of states and factors (40 KiB x ceil((nx-1)/1024) per point): sweep fewer points per call";
     return RT_ERR_UNSUPPORTED;
   }
-  *plan = FomPlan{m, parts, scratch};
+  *plan = FomPlan{m, parts, scratch, per_point};
   return RT_OK;
 }
 
-}  // namespace
-
-int rt_p1_fom_bdf_sweep_plan_info(int num_cus, const rt_fom_desc* desc, int64_t ld_step, int64_t stride_mu, int64_t* info3) {
+int fom_plan_info(int num_cus, const rt_fom_desc* desc, int64_t ld_step, int64_t stride_mu, bool certified, int64_t* out) {
   if (num_cus <= 0) return RT_ERR_ARG;
   FomPlan plan;
   const char* why = nullptr;
   static const double some_out = 0.0;   // the plan query has no output buffers: the checks only see that they are not null
   static const int some_info = 0;
-  RT_TRY(fom_plan(desc, &some_out, ld_step, stride_mu, &some_info, &plan, &why));
-  if (info3) {
-    info3[0] = desc->n_mu;
-    info3[1] = plan.parts;
-    info3[2] = plan.m;
+  RT_TRY(fom_plan(desc, &some_out, ld_step, stride_mu, &some_info, certified, &plan, &why));
+  if (out) {
+    out[0] = desc->n_mu;
+    out[1] = plan.parts;
+    out[2] = plan.m;
+    if (certified) out[3] = (int64_t)plan.per_point;
   }
   return RT_OK;
 }
 
-int rt_p1_fom_bdf_sweep(rt_ctx* ctx, const rt_fom_desc* desc, double* U_out, int64_t ld_step, int64_t stride_mu, int* info) {
+template <bool CERT>
+int fom_launch(rt_ctx* ctx, const rt_fom_desc* desc, double* U_out, int64_t ld_step, int64_t stride_mu, double defect_tol,
+               double* defect, int* info) {
   if (!ctx) return RT_ERR_ARG;
   FomPlan plan;
   const char* why = nullptr;
-  const int rc = fom_plan(desc, U_out, ld_step, stride_mu, info, &plan, &why);
+  const int rc = fom_plan(desc, U_out, ld_step, stride_mu, info, CERT, &plan, &why);
   if (rc != RT_OK) {
     ctx->err = why;
     return rc;
+  }
+  if (CERT && (!defect || !(defect_tol >= 0.0))) {   // a NaN tolerance fails the comparison too
+    ctx->err = "bad argument: defect && defect_tol >= 0";
+    return RT_ERR_ARG;
   }
   void* scratch = nullptr;
   RT_TRY(rt_scratch(ctx, plan.scratch, &scratch));
@@ -354,11 +473,33 @@ int rt_p1_fom_bdf_sweep(rt_ctx* ctx, const rt_fom_desc* desc, double* U_out, int
   p.U = U_out;
   p.info = info;
   p.arena = static_cast<double*>(scratch);
-  RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&p1_fom_kernel), FOM_LDS_BYTES));
-  hipLaunchKernelGGL(p1_fom_kernel, dim3((unsigned)desc->n_mu), dim3(FOM_THREADS), FOM_LDS_BYTES, ctx->stream, p);
+  p.defect_tol = defect_tol;
+  p.defect = defect;
+  RT_TRY(rt_func_lds(ctx, reinterpret_cast<const void*>(&p1_fom_kernel<CERT>), FOM_LDS_BYTES));
+  hipLaunchKernelGGL(p1_fom_kernel<CERT>, dim3((unsigned)desc->n_mu), dim3(FOM_THREADS), FOM_LDS_BYTES, ctx->stream, p);
   RT_HIP_CHECK(ctx, hipGetLastError());
   ctx->last_grid = desc->n_mu;
   ctx->last_splits = plan.parts;
   ctx->last_tile = plan.m;
   return RT_OK;
+}
+
+}  // namespace
+
+int rt_p1_fom_bdf_sweep_plan_info(int num_cus, const rt_fom_desc* desc, int64_t ld_step, int64_t stride_mu, int64_t* info3) {
+  return fom_plan_info(num_cus, desc, ld_step, stride_mu, false, info3);
+}
+
+int rt_p1_fom_bdf_sweep_certified_plan_info(int num_cus, const rt_fom_desc* desc, int64_t ld_step, int64_t stride_mu,
+                                            int64_t* info4) {
+  return fom_plan_info(num_cus, desc, ld_step, stride_mu, true, info4);
+}
+
+int rt_p1_fom_bdf_sweep(rt_ctx* ctx, const rt_fom_desc* desc, double* U_out, int64_t ld_step, int64_t stride_mu, int* info) {
+  return fom_launch<false>(ctx, desc, U_out, ld_step, stride_mu, 0.0, nullptr, info);
+}
+
+int rt_p1_fom_bdf_sweep_certified(rt_ctx* ctx, const rt_fom_desc* desc, double* U_out, int64_t ld_step, int64_t stride_mu,
+                                  double defect_tol, double* defect, int* info) {
+  return fom_launch<true>(ctx, desc, U_out, ld_step, stride_mu, defect_tol, defect, info);
 }

@@ -1,6 +1,8 @@
 """Full-order trajectories of the closed-form 1-D P1 models on the device: what ``fom.solve()`` computes one parameter
 point and one time step at a time on the host (testing/mock.py; the reference's ``OneDimensionalSolver.solve``,
-fom/base.py:693-831) for a whole sampling space in one kernel launch (``ops.p1_fom_bdf_sweep``, rt_p1_fom_bdf_sweep).
+fom/base.py:693-831) for a whole sampling space in one kernel launch (``ops.p1_fom_bdf_sweep``, rt_p1_fom_bdf_sweep; or
+``ops.p1_fom_bdf_sweep_certified``, which holds every step to a measured backward error where the rows are not
+diagonally dominant - the convection-dominated piston).
 
 The full-order model describes itself through ``p1_fom_recipe(mus, ts)`` (a table of seven scalars per step and point,
 two flags and the lifting ramp).  The snapshots stay on the device as ``(n_mu, nt, N_h)`` blocks whose ``[j].T`` is the
@@ -26,11 +28,28 @@ def recipe(fom, mus):
     return fom.p1_fom_recipe(list(mus), _times(fom))
 
 
-def fom_sweep(fom, mus, chunk=None, rec=None):
+CHECKS = ("dominance", "defect")
+DEFECT_TOL = 1e-10        # the relative residual the reference accepts for a linear solve (GMRES_OPTIONS, rom.py:36)
+
+
+def fom_sweep(fom, mus, chunk=None, rec=None, check="dominance", defect_tol=None, report=None):
     """Generator over ``(first_step, U_block)``: the homogeneous snapshots of every mu for steps first_step ..
     first_step + U_block.shape[1] - 1 as an (n_mu, steps, N_h) device tensor.  ``chunk`` = steps per kernel call (None: the
     whole horizon in one); the two last states are carried from call to call, and the snapshots do not depend on how the
-    horizon is cut.  A point whose system lost diagonal dominance or met a non-finite pivot raises ArithmeticError."""
+    horizon is cut.
+
+    ``check`` says what a step is trusted by.  "dominance": every row diagonally dominant, |d| >= |l| + |u| - which holds
+    only where about |w| dt/h <= 2 bdf/3 + 2 alpha dt/h^2 (a CFL number below one or a cell Peclet number below two).
+    "defect": the componentwise backward error of every step's solve, measured on the device
+    (``ops.p1_fom_bdf_sweep_certified``), at most ``defect_tol`` (None: 1e-10); the snapshots are the same bits, and
+    ``report`` (a dict) receives ``report["defect"]``, the (n_mu, nt) NumPy array of the steps swept so far.  A point that
+    fails the check, or meets a non-finite pivot, raises ArithmeticError."""
+    if check not in CHECKS:
+        raise ValueError(f"check must be 'dominance' or 'defect', not {check!r}")
+    certified = check == "defect"
+    tol = DEFECT_TOL if defect_tol is None else float(defect_tol)
+    if not tol >= 0.0:
+        raise ValueError(f"defect_tol must be a non-negative number, not {defect_tol!r}")
     mus = list(mus)
     rec = recipe(fom, mus) if rec is None else rec
     tab = ops.to_device(rec["tab"])
@@ -46,15 +65,28 @@ def fom_sweep(fom, mus, chunk=None, rec=None):
         if need > free:
             raise MemoryError(f"a block of {steps} steps for {n_mu} parameter points of {Nh} dofs takes {need} bytes and "
                               f"{free} are free on the device: pass a smaller `chunk` (steps per call)")
+    if certified and report is not None:
+        report["defect"] = np.zeros((n_mu, 0))
     u_init = None
     for first in range(0, nt, steps):
-        U, info = ops.p1_fom_bdf_sweep(fom.nx, tab[first:first + steps], fom.dt, rec["bdf2"], rec["state_in_w"], u_init=u_init,
-                                       first_step=first)
+        if certified:
+            U, info, defect = ops.p1_fom_bdf_sweep_certified(fom.nx, tab[first:first + steps], fom.dt, rec["bdf2"], rec["state_in_w"],
+                                                             u_init=u_init, first_step=first, defect_tol=tol)
+            defect = defect.cpu().numpy()
+            if report is not None:
+                report["defect"] = np.concatenate([report["defect"], defect], axis=1)
+        else:
+            U, info = ops.p1_fom_bdf_sweep(fom.nx, tab[first:first + steps], fom.dt, rec["bdf2"], rec["state_in_w"], u_init=u_init,
+                                           first_step=first)
         flags = info.cpu().numpy()
         if flags.any():
             j = int(np.flatnonzero(flags)[0])
+            step = int(flags[j]) - 1
+            if certified:
+                raise ArithmeticError(f"full-order sweep: mu = {mus[j]} has a backward error (defect) of {defect[j, step - first]:.3e} "
+                                      f"at step {step}, above defect_tol = {tol:.3e} or not finite")
             raise ArithmeticError(f"full-order sweep: mu = {mus[j]} has a row that is not diagonally dominant or a pivot that "
-                                  f"is not finite at step {int(flags[j]) - 1}")
+                                  f"is not finite at step {step}")
         if first + steps < nt:
             older = U[:, -2] if U.shape[1] > 1 else (u_init[:, 0] if u_init is not None else torch.zeros_like(U[:, -1]))
             u_init = torch.stack([U[:, -1], older], dim=1)

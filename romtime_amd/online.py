@@ -439,7 +439,8 @@ def evaluate(rom, srom, mus, which, fom_solutions=None, gamma=1.4, probes=None, 
         U = [None if full is None else homogeneous(j, full) for j, full in enumerate(stored)]
         need = [j for j, full in enumerate(stored) if full is None]
         if need and hasattr(fom, "p1_fom_recipe"):
-            (_, block), = device_fom.fom_sweep(fom, [part[j] for j in need])      # (n_need, nt, N_h), homogeneous
+            (_, block), = device_fom.fom_sweep(fom, [part[j] for j in need],      # (n_need, nt, N_h), homogeneous
+                                               check=getattr(rom, "FOM_CHECK", "dominance"))
             for k, j in enumerate(need):
                 U[j] = block[k].T
         else:

@@ -533,6 +533,46 @@ def p1_fom_bdf_sweep(nx: int, tab, dt: float, bdf2: bool, state_in_w: bool, u_in
     return out, info
 
 
+def p1_fom_plan_info_certified(nx: int, n_mu: int = 1, nt: int = 1, num_cus: int = 256):
+    """(workgroups, partitions per system, rows per partition, scratch bytes per point) of
+    ``p1_fom_bdf_sweep_certified`` - the twin of ``p1_fom_plan``, host logic only
+    (rt_p1_fom_bdf_sweep_certified_plan_info)."""
+    lib = _lib.load()
+    Nh = int(nx) + 1
+    tab = (C.c_double * 7)()   # the checks only see that the table is there
+    desc = _lib.FomDesc(int(nx), int(n_mu), int(nt), 0, 1.0, 0, 0, C.cast(tab, _p), None)
+    info4 = (C.c_int64 * 4)()
+    rc = lib.rt_p1_fom_bdf_sweep_certified_plan_info(int(num_cus), C.byref(desc), Nh, int(nt) * Nh, info4)
+    if rc != 0:
+        raise RomtimeHipError(f"rt_p1_fom_bdf_sweep_certified_plan_info failed ({rc}) for nx = {nx}, n_mu = {n_mu}, nt = {nt}")
+    return int(info4[0]), int(info4[1]), int(info4[2]), int(info4[3])
+
+
+def p1_fom_bdf_sweep_certified(nx: int, tab, dt: float, bdf2: bool, state_in_w: bool, u_init: torch.Tensor = None,
+                               first_step: int = 0, defect_tol: float = 1e-10):
+    """``p1_fom_bdf_sweep`` - the same solve, the same bits in U - certified by the backward error of every step instead of
+    by diagonal dominance.  Returns ``(U, info, defect)``: defect (n_mu, nt) float64, the componentwise backward error of
+    every step's solve (+inf where a pivot or a state value was not finite), and info (n_mu int32): 0, or 1 + the global
+    step of the first defect that is not finite or above ``defect_tol``.  rt_p1_fom_bdf_sweep_certified."""
+    ctx = Context.current()
+    tab = to_device(tab).contiguous()
+    if tab.dim() != 3 or tab.shape[2] != 7:
+        raise RomtimeHipError("p1_fom_bdf_sweep_certified: `tab` must be (nt, n_mu, 7)")
+    nt, n_mu, Nh = int(tab.shape[0]), int(tab.shape[1]), int(nx) + 1
+    if u_init is not None:
+        u_init = to_device(u_init).contiguous()
+        if tuple(u_init.shape) != (n_mu, 2, Nh):
+            raise RomtimeHipError(f"p1_fom_bdf_sweep_certified: `u_init` must be (n_mu, 2, {Nh})")
+    out = torch.empty((n_mu, nt, Nh), dtype=torch.float64, device=tab.device)
+    info = torch.empty(n_mu, dtype=torch.int32, device=tab.device)
+    defect = torch.empty((n_mu, nt), dtype=torch.float64, device=tab.device)
+    desc = _lib.FomDesc(int(nx), n_mu, nt, int(first_step), float(dt), int(bool(bdf2)), int(bool(state_in_w)), _ptr(tab),
+                        _ptr(u_init))
+    ctx.check(ctx.lib.rt_p1_fom_bdf_sweep_certified(ctx.handle, C.byref(desc), _ptr(out), Nh, nt * Nh, float(defect_tol),
+                                                    _ptr(defect), _ptr(info)), "rt_p1_fom_bdf_sweep_certified")
+    return out, info, defect
+
+
 def sym_eig_values(G: torch.Tensor, first: int = 0, count: int | None = None):
     """Eigenvalues (descending, device) of the symmetric n x n G; (lam, status).  With ``first`` / ``count`` only
     lam[first:first+count] is computed (the rest of ``lam`` is left unset).  rt_sym_eig_values(_part)."""

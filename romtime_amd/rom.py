@@ -52,6 +52,11 @@ class RomConstructor(Reductor):
     # (``romtime_amd.fom``, rt_p1_fom_bdf_sweep) for a FOM that describes itself through ``p1_fom_recipe``; its snapshots
     # differ from the host loop's by rounding, so the caller chooses.
     SNAPSHOTS_ON = "host"
+    # What the device full-order sweeps (SNAPSHOTS_ON = "device", the FOM truth of ``online.evaluate``) trust a step by.
+    # "dominance": every row diagonally dominant - a CFL number below one or a cell Peclet number below two.  "defect":
+    # the measured backward error of every step's solve at most 1e-10 (``fom.fom_sweep(check="defect")``,
+    # rt_p1_fom_bdf_sweep_certified) - the convection-dominated piston; ``fom_defects[mu_idx]`` keeps the (nt,) defects.
+    FOM_CHECK = "dominance"
     # Where ``solve`` / ``solve_many`` run.  "host": the reference's loop, one FOM callback per operator and step.
     # "device": the whole BDF loop of all points in one sweep (``romtime_amd.online``, rt_hrom_bdf_sweep) for a model whose
     # operators are all hyper-reduced or whose FOM is affine (``online.plan``); its trajectories differ from the host
@@ -64,6 +69,7 @@ class RomConstructor(Reductor):
         self.name = name
         self.basis = None
         self.basis_nonlinear = None
+        self.fom_defects = dict()
         self.solutions = dict()
         self.errors = dict()
         self.exact = dict()
@@ -132,6 +138,7 @@ class RomConstructor(Reductor):
         truncated.REDUCED_SOLVER = self.REDUCED_SOLVER
         truncated.GMRES_OPTIONS = deepcopy(self.GMRES_OPTIONS)
         truncated.ONLINE_ON = self.ONLINE_ON
+        truncated.FOM_CHECK = self.FOM_CHECK
         truncated.setup(rnd=self.random_state)
         N = self.N
         assert n < N, "You want to remove too many modes from S-ROM to create ROM."
@@ -204,10 +211,13 @@ class RomConstructor(Reductor):
 
             mus = [self.add_mu(mu=mu, step=Stage.OFFLINE) for mu in space]
             rec = device_fom.recipe(fom, [mu for _, mu in mus])
-            (_, U), = device_fom.fom_sweep(fom, [mu for _, mu in mus], rec=rec)
+            swept = dict()
+            (_, U), = device_fom.fom_sweep(fom, [mu for _, mu in mus], rec=rec, check=self.FOM_CHECK, report=swept)
             full = device_fom.full_solution(U, rec["lift"])
             for j, (mu_idx, mu) in enumerate(mus):
                 fom_solutions[mu_idx] = full[j].T.cpu().numpy()
+                if "defect" in swept:
+                    self.fom_defects[mu_idx] = swept["defect"][j].copy()
                 tags.append((mu_idx, False))
                 yield U[j].T
                 if rec["state_in_w"]:
@@ -216,6 +226,8 @@ class RomConstructor(Reductor):
 
         if self.SNAPSHOTS_ON not in ("host", "device"):
             raise ValueError(f"SNAPSHOTS_ON must be 'host' or 'device', not {self.SNAPSHOTS_ON!r}")
+        if self.FOM_CHECK not in ("dominance", "defect"):
+            raise ValueError(f"FOM_CHECK must be 'dominance' or 'defect', not {self.FOM_CHECK!r}")
         if self.SNAPSHOTS_ON == "device":
             if not hasattr(fom, "p1_fom_recipe"):
                 raise NotImplementedError(f"SNAPSHOTS_ON = 'device' needs a full-order model with p1_fom_recipe(mus, ts); "

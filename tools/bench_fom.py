@@ -7,7 +7,12 @@ Per problem: the host loop timed over ``--host-steps`` steps of ``--host-points`
 assembly + SuperLU per step); the distances d_host and d_dev of both routes from the long-double recipe over those steps
 (relative L2 over the block, tests/fom_cases.py); the device sweep over ``--steps`` steps for 1, 32 and 256 parameter
 points, device-event times of ``--reps`` launches after a warm-up (median, min, max).  Writes a table and one JSON line
-per problem to ``--out`` and prints the JSON lines."""
+per problem to ``--out`` and prints the JSON lines.
+
+``--piston`` measures the convection-dominated row instead and APPENDS it to ``--out``: MockBurgers at the sizes of the
+reference's piston runs (nt = 100, T = 1, alpha_0 = 1e-6, delta = 0.1, omega = 6; tests/fom_defect_cases.py) at ``--nx``
+cells, where every step loses diagonal dominance - the dominance entry beside ``ops.p1_fom_bdf_sweep_certified``, the
+worst reported defect, and the cost of the defect pass per step."""
 import argparse
 import json
 import os
@@ -34,6 +39,37 @@ def timed(fn, reps):
     return out
 
 
+def piston_row(a):
+    """The convection-dominated row: both entries on the same table, 1, 32 and 256 points."""
+    from tests import fom_defect_cases as dc
+
+    fom = dc.make_fom(a.nx, 100, True, T=1.0)
+    mu = dict(dc.CONV_MUS[0])
+    lines = [f"piston sizes, nx = {a.nx}, nt = 100, T = 1, alpha_0 = 1e-6 (BDF2), median of {a.reps} launches (min - max), ms for 100 steps",
+             "points   dominance entry          certified entry          defect pass us/step   flagged by dominance   worst defect   flagged by defect"]
+    raw = dict(problem="piston", nx=a.nx, nt=100, reps=a.reps, gpu=torch.cuda.get_device_name(0), device=[])
+    for n_mu in (1, 32, 256):
+        rec = fc.recipe(fom, [mu] * n_mu)
+        tab = ops.to_device(rec["tab"])
+        plain = lambda: ops.p1_fom_bdf_sweep(a.nx, tab, fom.dt, rec["bdf2"], rec["state_in_w"])
+        cert = lambda: ops.p1_fom_bdf_sweep_certified(a.nx, tab, fom.dt, rec["bdf2"], rec["state_in_w"])
+        _, flags = plain()
+        _, cflags, defect = cert()
+        torch.cuda.synchronize()
+        ms0, ms1 = timed(plain, a.reps), timed(cert, a.reps)
+        m0, m1 = float(np.median(ms0)), float(np.median(ms1))
+        dev = dict(points=n_mu, dominance_ms=ms0, certified_ms=ms1, dominance_median_ms=m0, certified_median_ms=m1,
+                   defect_pass_us_per_step=10.0 * (m1 - m0), flagged_by_dominance=int(flags.count_nonzero()),
+                   worst_defect=float(defect.max()), flagged_by_defect=int(cflags.count_nonzero()))
+        raw["device"].append(dev)
+        lines.append(f"{n_mu:6d}   {m0:8.2f} ({min(ms0):.2f} - {max(ms0):.2f})   {m1:8.2f} ({min(ms1):.2f} - {max(ms1):.2f})   "
+                     f"{dev['defect_pass_us_per_step']:19.1f}   {dev['flagged_by_dominance']:20d}   {dev['worst_defect']:.3e}   {dev['flagged_by_defect']:17d}")
+    print(json.dumps(raw), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "a") as fp:
+        fp.write("\n" + "\n".join(lines) + "\n\nraw: " + json.dumps(raw) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nx", type=int, default=100_000)
@@ -42,9 +78,12 @@ def main():
     ap.add_argument("--host-points", type=int, default=2)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=os.path.join("profiles", "fom_sweep_ab.txt"))
+    ap.add_argument("--piston", action="store_true", help="the convection-dominated row, both entries, appended to --out")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_fom.py measures on the GPU only")
+    if a.piston:
+        return piston_row(a)
     plan = ops.p1_fom_plan(a.nx)
     lines, raws = [], []
     lines.append("problem    host ms/step/point   host steps/s   d_host      d_dev       bar         | points   device ms (min - max) for "
