@@ -480,6 +480,41 @@ int rt_p1_fom_bdf_sweep_certified(rt_ctx* ctx, const rt_fom_desc* desc, double* 
 int rt_p1_fom_bdf_sweep_certified_plan_info(int num_cus, const rt_fom_desc* desc, int64_t ld_step, int64_t stride_mu,
                                             int64_t* info4);
 
+/* ---- residuals of lifted reduced trajectories in the full-order step system, since version 420: what the time loop of
+ *      OneDimensionalSolver.solve (fom/base.py:693-831) solves at every step, evaluated at x^t = B a_j[t] instead of
+ *      solved - an error indicator of an online sweep that needs no full-order solve and no second reduced model ---- */
+/* desc is the descriptor of rt_p1_fom_bdf_sweep for the same points and steps: nx, n_mu (the number of trajectories), nt,
+ * first_step, dt, bdf2, state_in_w, tab.  desc->u_init must be NULL: the two older states come as coefficients, a_init =
+ * NULL for a zero state (then first_step must be 0), else n_mu x 2 x k DEVICE, a^n and a^{n-1} of every trajectory.
+ * B: the (nx+1) x k row-major basis, ldb >= k, k <= 128 (RT_ERR_UNSUPPORTED beyond); A, lda, stride_a exactly as for
+ * rt_trajectory_errors (the uN_out of the sweeps goes in unchanged).  With the lifted states x^t = B a_j[t], whose values
+ * at the nodes 0 and nx are taken as 0 whatever B holds in those rows (the Dirichlet zeros the sweep writes), step s of
+ * trajectory j has the interior rows i = 1 .. nx-1 of rt_p1_fom_bdf_sweep, formed from the lifted states of the steps
+ * s-1 and s-2 with l_1 = u_{nx-1} = 0, and
+ *     r_i = fma(-u_i, x_{i+1}, fma(-d_i, x_i, fma(-l_i, x_{i-1}, rhs_i))),  s_i = |l_i x_{i-1}| + |d_i x_i| + |u_i x_{i+1}| + |rhs_i|,
+ *     res[j nt + s] = sqrt(sum_i r_i^2),   scale[j nt + s] = sqrt(sum_i s_i^2)     (n_mu x nt DEVICE each; scale may be NULL).
+ *   - res / scale is the 2-norm companion of the componentwise defect of rt_p1_fom_bdf_sweep_certified: a few eps for the
+ *     sweep's own trajectory (B = I), the size of the reduction and hyper-reduction error otherwise.
+ *   - A lifted value that is not finite makes res NaN or inf at the steps that read it - its own and, as an older state,
+ *     the two after it - and at no other step and in no other trajectory.
+ *   - Null desc, tab, B, A or res, a non-null desc->u_init, sizes < 1, nx < 2, ldb or lda < k and a_init == NULL with
+ *     first_step != 0 return RT_ERR_ARG before any launch; nx > 2^22 and k > 128 RT_ERR_UNSUPPORTED.
+ *   - The lifted trajectory is never stored: 32-row stages of B against a 64-step coefficient block on the f64 matrix
+ *     cores, as rt_trajectory_errors; the lifted tile goes through LDS, and a stage evaluates its inner 30 rows, a block
+ *     its last 62 steps.  No floating-point atomics: partial sums go to [trajectory][row slice][step] in the ctx's leaf
+ *     arena and a second kernel adds the slices in order.  The slicing depends on nx and the ctx's CU count only, so the
+ *     bits of a trajectory depend neither on n_mu, nor on its place in the batch, nor on how the horizon is cut into
+ *     calls (a_init = the two last coefficient rows of the call before).
+ *   - rt_last_launch_info: [0] workgroups, [1] row slices, [2] tile 30 rows x 62 steps (30062). */
+int rt_trajectory_residuals(rt_ctx* ctx, const rt_fom_desc* desc, const double* B, int64_t ldb, int64_t k, const double* A,
+                            int64_t lda, int64_t stride_a, const double* a_init, double* res, double* scale);
+/* The argument checks and the slicing of rt_trajectory_residuals for a ctx with num_cus CUs - host logic only, no GPU,
+ * and no pointer but desc is followed: the same return code, and on RT_OK info3 (may be NULL) as rt_last_launch_info
+ * reports it. */
+int rt_trajectory_residuals_plan_info(int num_cus, const rt_fom_desc* desc, const double* B, int64_t ldb, int64_t k,
+                                      const double* A, int64_t lda, int64_t stride_a, const double* a_init, const double* res,
+                                      const double* scale, int64_t* info3);
+
 /* ---- small symmetric eigenproblem of the Gram matrix, on the device (3 <= n <= 2048) ---------- */
 /* Householder tridiagonalisation (32 cooperating workgroups, 128 for n > 512; matrix resident in LDS) + Sturm
  * multisection:

@@ -85,6 +85,8 @@ SIGNATURES = {
     "rt_p1_fom_bdf_sweep_plan_info": (_int, [_int, _p, _i64, _i64, C.POINTER(_i64)]),
     "rt_p1_fom_bdf_sweep_certified": (_int, [_p, _p, _p, _i64, _i64, C.c_double, _p, _p]),
     "rt_p1_fom_bdf_sweep_certified_plan_info": (_int, [_int, _p, _i64, _i64, C.POINTER(_i64)]),
+    "rt_trajectory_residuals": (_int, [_p, _p, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _p]),
+    "rt_trajectory_residuals_plan_info": (_int, [_int, _p, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _p, C.POINTER(_i64)]),
     "rt_sym_eig_values": (_int, [_p, _p, _i64, _p, _p]),
     "rt_sym_eig_values_part": (_int, [_p, _p, _i64, _i64, _i64, _p, _p]),
     "rt_sym_eig_vectors": (_int, [_p, _i64, _i64, _p, _p]),

@@ -6,7 +6,10 @@
 Everything goes through ``ops.trajectory_errors`` (rt_trajectory_errors): the lifted trajectories ``V u_N`` are never
 stored.  Full-order snapshots are taken one parameter point at a time, NumPy or device tensors in either memory order;
 host arrays are uploaded one at a time and never held together here.  Results are NumPy arrays in the discrete l2 norm
-of the reference, ``||.||_2 / sqrt(N_h)``."""
+of the reference, ``||.||_2 / sqrt(N_h)``.
+
+``trajectory_residuals`` needs no full-order snapshots at all: it holds the lifted trajectories against the full-order
+step system itself (``ops.trajectory_residuals``, rt_trajectory_residuals), for FOMs that state it (``p1_fom_recipe``)."""
 from __future__ import annotations
 
 import numpy as np
@@ -155,3 +158,51 @@ def evaluate(V_rom, uN_rom, V_srom, uN_srom, U, lift=None):
             entry[Errors.SACRIFICIAL] = _host(ops.trajectory_errors(B_srom, A_srom[j], Ud))[0]
         out.append(entry)
     return out
+
+
+def trajectory_residuals(fom, V, uN, mus, rec=None, relative=True, chunk=None):
+    """Residuals of the reduced trajectories in the FULL-ORDER step system, with no full-order solve: for every point j
+    and step s, ``res = ||rhs - K x^s||_2`` and ``scale = || |K| |x^s| + |rhs| ||_2`` over the interior rows of the system
+    ``fom_sweep`` solves at that step, evaluated at the lifted states x^t = V uN[j, t] (the rows formed from x^{s-1} and
+    x^{s-2}, zero before the first step).  ``res / scale`` is a few eps for the full-order trajectory itself; for an
+    exact Galerkin model the residual is orthogonal to V, for a hyper-reduced one it is not, so the curve shows the
+    hyper-reduction error directly.
+
+    ``fom`` states its step system through ``p1_fom_recipe`` (NotImplementedError otherwise); ``rec`` is that recipe when
+    the caller already has it.  ``uN``: (len(mus), nt, r); ``V``: (nx + 1) x r, r <= 128.  Returns the (n_mu, nt) NumPy
+    array ``res / scale`` (0 where scale is 0), or the pair ``(res, scale)`` with ``relative=False``.  ``chunk`` = steps
+    per kernel call (None: the whole horizon in one); the two last coefficient rows are carried from call to call, and
+    the result does not depend on how the horizon is cut."""
+    from . import fom as device_fom
+
+    mus = list(mus)
+    rec = device_fom.recipe(fom, mus) if rec is None else rec
+    B = ops.to_device(V)
+    A = ops.to_device(uN)
+    tab = ops.to_device(rec["tab"])
+    nx = int(fom.nx)
+    nt = int(tab.shape[0])
+    if B.dim() != 2 or B.shape[0] != nx + 1:
+        raise ValueError(f"the basis must be (nx + 1) x r = {nx + 1} x r, not {tuple(B.shape)}")
+    if B.shape[1] > MAX_COLUMNS:
+        raise ValueError(f"{B.shape[1]} basis columns: at most {MAX_COLUMNS}")
+    if tuple(A.shape) != (len(mus), nt, B.shape[1]):
+        raise ValueError(f"uN must be (n_mu, nt, r) = {(len(mus), nt, int(B.shape[1]))}, not {tuple(A.shape)}")
+    if int(tab.shape[1]) != len(mus):
+        raise ValueError(f"the recipe's table is for {int(tab.shape[1])} parameter points, not {len(mus)}")
+    steps = nt if chunk is None else int(chunk)
+    if steps < 1:
+        raise ValueError(f"chunk must be a positive number of steps, not {chunk!r}")
+    res, scale = np.empty((len(mus), nt)), np.empty((len(mus), nt))
+    a_init = None
+    for first in range(0, nt, steps):
+        block = A[:, first:first + steps]
+        r, s = ops.trajectory_residuals(B, block, nx, tab[first:first + steps], fom.dt, rec["bdf2"], rec["state_in_w"],
+                                        a_init=a_init, first_step=first)
+        res[:, first:first + steps], scale[:, first:first + steps] = _host(r), _host(s)
+        older = block[:, -2] if block.shape[1] > 1 else (a_init[:, 0] if a_init is not None else torch.zeros_like(block[:, -1]))
+        a_init = torch.stack([block[:, -1], older], dim=1)
+    if not relative:
+        return res, scale
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(scale == 0.0, 0.0, res / np.where(scale == 0.0, 1.0, scale))

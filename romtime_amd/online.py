@@ -389,11 +389,12 @@ class Evaluation(dict):
     closed forms, ``mass`` = ``{idx_mu: {ProblemType.ROM: payload, ProblemType.FOM: payload}}`` (hrom.py:604-621) and
     ``probes`` = ``{idx_mu: (nt, len(x))}`` of the ROM; both are empty dicts otherwise.  ``solutions`` holds what
     ``solve_many`` returned per chunk, ``{ProblemType.ROM: [...], ProblemType.SROM: [...]}`` (reduced trajectories and
-    storages on demand: nothing of size N_h x nt)."""
+    storages on demand: nothing of size N_h x nt).  ``residuals`` = ``{idx_mu: {ProblemType.ROM: curve, ProblemType.SROM:
+    curve}}``, the full-order residual curves of ``certify.trajectory_residuals``, when asked for (empty otherwise)."""
 
     def __init__(self):
         super().__init__()
-        self.mass, self.probes = {}, {}
+        self.mass, self.probes, self.residuals = {}, {}, {}
         self.solutions = {ProblemType.ROM: [], ProblemType.SROM: []}
 
 
@@ -403,7 +404,19 @@ def _is_piston(fom, mus, ts):
             and "lift" in fom.p1_closed_form(mus[:1], ts[:1]))
 
 
-def evaluate(rom, srom, mus, which, fom_solutions=None, gamma=1.4, probes=None, chunk=None) -> Evaluation:
+def residuals(rom, mus, which) -> dict:
+    """``{idx_mu: curve}``: ``rom.solve_many(mus, step=which)`` and the relative full-order residual of every step of every
+    reduced trajectory (``certify.trajectory_residuals``).  No full-order solve is made: the FOM states its step system
+    through ``p1_fom_recipe`` (NotImplementedError otherwise)."""
+    from . import certify
+
+    mus = list(mus)
+    sol = rom.solve_many(mus, step=which)
+    curves = certify.trajectory_residuals(rom.fom, sol._V, sol.uN, mus)
+    return {i: curves[j] for j, i in enumerate(sol.idx)}
+
+
+def evaluate(rom, srom, mus, which, fom_solutions=None, gamma=1.4, probes=None, chunk=None, residuals=False) -> Evaluation:
     """``HyperReducedPiston._evaluate`` (hrom.py:504-621) as one call: ``solve_many`` on the ROM and the S-ROM, the FOM
     truth of every point - ``fom_solutions[idx]`` (the validation storage, full solutions N_h x nt), else one device sweep
     of the chunk when the FOM has ``p1_fom_recipe``, else the host ``fom.solve()`` - and the three error curves per point
@@ -411,7 +424,9 @@ def evaluate(rom, srom, mus, which, fom_solutions=None, gamma=1.4, probes=None, 
     compared (a stored full solution has its lifting taken off) and the lifting is added only where an output needs it:
     the mass-conservation payloads of the piston problem (``outputs.mass_conservation`` for the ROM,
     ``outputs.snapshot_mass_conservation`` for the FOM) and ``outputs.probes`` at the positions ``probes``.  Points go in
-    chunks of ``chunk`` (None: all at once); no N_h x nt matrix of a point outlives its chunk."""
+    chunks of ``chunk`` (None: all at once); no N_h x nt matrix of a point outlives its chunk.  ``residuals=True`` adds,
+    for a FOM with ``p1_fom_recipe``, ``result.residuals[idx]``: the full-order residual curves of both models
+    (``certify.trajectory_residuals``)."""
     from . import certify, outputs
     from . import fom as device_fom
 
@@ -451,6 +466,12 @@ def evaluate(rom, srom, mus, which, fom_solutions=None, gamma=1.4, probes=None, 
                 U[j] = homogeneous(j, fom.solutions.fom)
         for j, payload in enumerate(certify.evaluate(sol._V, sol.uN, ssol._V, ssol.uN, U)):
             result[sol.idx[j]] = payload
+        if residuals and hasattr(fom, "p1_fom_recipe"):
+            rec = device_fom.recipe(fom, part)
+            curves = {kind: certify.trajectory_residuals(fom, s._V, s.uN, part, rec=rec)
+                      for kind, s in ((ProblemType.ROM, sol), (ProblemType.SROM, ssol))}
+            for j in range(len(part)):
+                result.residuals[sol.idx[j]] = {kind: c[j] for kind, c in curves.items()}
         if _is_piston(fom, part, ts):
             L = np.ascontiguousarray(np.asarray(fom.p1_closed_form(part, ts)["h"]).T) * int(fom.nx)      # (n_mu, nt)
             mass = outputs.mass_conservation(rom.basis, sol.uN, part, dt, L, gamma=gamma, lift=lift, ts=ts)

@@ -573,6 +573,62 @@ def p1_fom_bdf_sweep_certified(nx: int, tab, dt: float, bdf2: bool, state_in_w: 
     return out, info, defect
 
 
+def trajectory_residuals_plan(nx: int, k: int = 1, nt: int = 1, n_traj: int = 1, num_cus: int = 256):
+    """(workgroups, row slices, tile) of ``trajectory_residuals`` for nx cells on a ctx of ``num_cus`` CUs - host logic
+    only, no GPU (rt_trajectory_residuals_plan_info); tile = 1000 x rows a stage evaluates + steps a block evaluates.
+    Raises where the call would refuse the sizes."""
+    lib = _lib.load()
+    some = (C.c_double * 7)()   # the checks only see that the operands are there
+    desc = _lib.FomDesc(int(nx), int(n_traj), int(nt), 0, 1.0, 0, 0, C.cast(some, _p), None)
+    info3 = (C.c_int64 * 3)()
+    sp = C.cast(some, _p)
+    rc = lib.rt_trajectory_residuals_plan_info(int(num_cus), C.byref(desc), sp, int(k), int(k), sp, int(k), int(nt) * int(k), None,
+                                               sp, None, info3)
+    if rc != 0:
+        raise RomtimeHipError(f"rt_trajectory_residuals_plan_info failed ({rc}) for nx = {nx}, k = {k}, nt = {nt}, "
+                              f"n_traj = {n_traj}")
+    return int(info3[0]), int(info3[1]), int(info3[2])
+
+
+def trajectory_residuals(V: torch.Tensor, uN: torch.Tensor, nx: int, tab, dt: float, bdf2: bool, state_in_w: bool,
+                         a_init: torch.Tensor = None, first_step: int = 0):
+    """Residuals of the lifted trajectories x^t = V uN[j, t] in the full-order step system of ``p1_fom_bdf_sweep``, without
+    storing them and without a full-order solve (rt_trajectory_residuals).  V: (nx + 1) x k basis (k <= 128; its rows 0
+    and nx are not looked at: the lifted values there are 0); uN: (nt, k) or (n, nt, k) coefficients, as the sweeps return
+    them; ``tab`` (nt, n, 7), dt and the flags as for ``p1_fom_bdf_sweep``; ``a_init`` (n, 2, k): the coefficients of the
+    two steps before ``first_step`` (newest first), None = zero states.  Returns ``(res, scale)``, (n, nt) each:
+    res[j, s] = ||rhs - K x^s||_2 over the interior rows of step s, scale[j, s] = || |K| |x^s| + |rhs| ||_2."""
+    ctx = Context.current()
+    tab = to_device(tab).contiguous()
+    for name, t in (("V", V), ("uN", uN), ("a_init", a_init)):
+        if t is not None and (t.dtype != torch.float64 or not t.is_cuda):
+            raise RomtimeHipError(f"trajectory_residuals: {name} must be a float64 CUDA tensor")
+    if V.dim() != 2 or uN.dim() not in (2, 3):
+        raise RomtimeHipError("trajectory_residuals: V must be 2-D, uN 2-D or 3-D")
+    if uN.dim() == 2:
+        uN = uN.unsqueeze(0)
+    Nh, k = V.shape
+    n, nt, k2 = uN.shape
+    if Nh != int(nx) + 1 or k2 != k or tab.dim() != 3 or tuple(tab.shape) != (nt, n, 7):
+        raise RomtimeHipError(f"trajectory_residuals: shapes do not match (nx = {nx}, V {tuple(V.shape)}, uN {tuple(uN.shape)}, "
+                              f"tab {tuple(tab.shape)})")
+    if a_init is not None:
+        a_init = a_init.contiguous()
+        if tuple(a_init.shape) != (n, 2, k):
+            raise RomtimeHipError(f"trajectory_residuals: `a_init` must be ({n}, 2, {k})")
+    if _layout_last2(V) is None or _layout_last2(V)[1] != ROW_MAJOR:
+        V = V.contiguous()
+    if _layout_last2(uN) is None or _layout_last2(uN)[1] != ROW_MAJOR:
+        uN = uN.contiguous()
+    ldb, lda = _layout_last2(V)[0], _layout_last2(uN)[0]
+    res = torch.empty((n, nt), dtype=torch.float64, device=V.device)
+    scale = torch.empty((n, nt), dtype=torch.float64, device=V.device)
+    desc = _lib.FomDesc(int(nx), n, nt, int(first_step), float(dt), int(bool(bdf2)), int(bool(state_in_w)), _ptr(tab), None)
+    ctx.check(ctx.lib.rt_trajectory_residuals(ctx.handle, C.byref(desc), _ptr(V), ldb, k, _ptr(uN), lda, uN.stride(0),
+                                              _ptr(a_init), _ptr(res), _ptr(scale)), "rt_trajectory_residuals")
+    return res, scale
+
+
 def sym_eig_values(G: torch.Tensor, first: int = 0, count: int | None = None):
     """Eigenvalues (descending, device) of the symmetric n x n G; (lam, status).  With ``first`` / ``count`` only
     lam[first:first+count] is computed (the rest of ``lam`` is left unset).  rt_sym_eig_values(_part)."""
