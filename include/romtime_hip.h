@@ -98,6 +98,13 @@ int rt_last_gram_ms(rt_ctx* ctx, double* ms);
  * per off-diagonal / diagonal tile and XCD), 2 one launch with uniform slots (out[1] / out[2] per tile) whose paced
  * workgroups read the snapshots once. */
 int rt_gram_plan_info(int num_cus, int64_t n_rows, int64_t n_cols, int* out);
+/* The slot plan of one launch of the two-launch form (since version 430; host logic only): launch 0 the off-diagonal
+ * tiles, 1 the diagonal ones, for the row range of XCD xcd (0..7).  out[0] = tiles of the launch, out[1] = regular slots
+ * per tile (stage q, q + out[1], ... below out[4]), out[2] = spare slots in use (0: the plain launch), out[3] = most tails
+ * per spare slot (spare slot j takes the stages [out[4], out[5]) of out[0] / out[2] consecutive tiles, the first
+ * out[0] % out[2] spare slots one tile more), out[4] = n_main, out[5] = 16-row stages of the range.  RT_ERR_UNSUPPORTED
+ * where rt_gram_plan_info gives another form or the launch has no tile. */
+int rt_gram_spare_plan_info(int num_cus, int64_t n_rows, int64_t n_cols, int launch, int xcd, int* out);
 
 /* ---- POD (src/romtime/rom/pod.py:7-62) ------------------------------------------------ */
 

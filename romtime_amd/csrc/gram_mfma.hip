@@ -13,7 +13,13 @@
 //    executed/algorithmic flops 0.80 -> 0.97 at n = 512.  They run as a second launch of a
 //    DIAG instantiation (72 accumulator VGPRs instead of 128, A panel only), each launch with
 //    its own number of sub-splits so that it fills the chip evenly.
-//
+//  * Spare slots take the tiles' tails.  n_t tiles with s slots each rarely fill an XCD's slots (the pipeline's 56: 6
+//    off-diagonal tiles x 9 = 54; 64 at n = 640: 10 x 6 = 60).  The R slots left over get workgroups of their own: every
+//    regular slot stops at stage n_main of the XCD's range, and the stages behind it - the tile's tail - go whole to a
+//    spare slot, which sweeps its at most ceil(n_t / R) tails one after the other into one more slab per tile
+//    (gram_spare_plan()).  n_main makes a regular and a full spare slot equally long.  Short sets, where the 48-stage
+//    floor and not the slot count limits s, keep the plain launch bit for bit.  Measured on the pipeline's off-diagonal
+//    launch: 3.50 -> 3.39 ms (profiles/gram_spare_slots_ab.txt).
 //
 //  * ONE launch for long snapshot sets where the slot model says it pays (gram_choose()).  The two launches each sweep
 //    all of X (8.2 GB of HBM reads at best, 13 GB measured in the pipeline).  In the one-launch form every off-diagonal
@@ -52,7 +58,12 @@ struct GramParams {
   long* counters;      // rt_ctx::dev_counters
   unsigned long long* pace;  // this launch's progress counters ([8 XCDs][16]: {stages done, workgroups started}), or nullptr
   int pace_every, pace_slack, pace_naps;   // check every so many stages; lead allowed (stages of its own); naps per check
-  unsigned char slot_tm[MAX_SLOTS], slot_tn[MAX_SLOTS], slot_q[MAX_SLOTS], slot_S[MAX_SLOTS];
+  // Two launches: slots below n_regular take stages q, q + S, ... below n_main[x] of XCD x's range and write slab
+  // slot_slab; the spare slots behind them take the tails [n_main[x], end) of slot_tn tiles from tile slot_tm on, one after
+  // the other (gram_spare_plan()).  Without spare slots n_regular is the grid's slot count and n_main[x] the whole range.
+  int n_regular;
+  int n_main[8];
+  unsigned char slot_tm[MAX_SLOTS], slot_tn[MAX_SLOTS], slot_q[MAX_SLOTS], slot_S[MAX_SLOTS], slot_slab[MAX_SLOTS];
 };
 
 // One launch (gram128_merged_kernel): the tile, stage offset and stride of every slot and the slab it writes.
@@ -70,11 +81,18 @@ struct GramSegs {
 __device__ const unsigned char kDiagTi[8][5] = {{0, 0, 0, 0, 0}, {0, 0, 0, 1, 1}, {1, 1, 1, 1, 1}, {2, 2, 2, 2, 2}, {2, 3, 3, 3, 255}, {3, 3, 4, 4, 255}, {4, 4, 5, 5, 255}, {5, 6, 6, 7, 255}};
 __device__ const unsigned char kDiagTj[8][5] = {{0, 1, 2, 3, 4}, {5, 6, 7, 1, 2}, {3, 4, 5, 6, 7}, {2, 3, 4, 5, 6}, {7, 3, 4, 5, 0}, {6, 7, 4, 5, 0}, {6, 7, 5, 6, 0}, {7, 6, 7, 7, 0}};
 
-// One slot's work: the 128 x 128 tile (tm, tn) of X^T X over the stages q0, q0 + S, ... of XCD x's K range, written to
-// `out` (a 128 x 128 slab).  All arguments are wave-uniform (SGPRs).
+// Stages (16 rows each) of XCD x's K range; the last one may be partial, the last XCD's range is the shortest.
+__device__ __forceinline__ int gram_range_stages(const GramParams& p, int x) {
+  const long kbeg = (long)x * p.kx, kend = (kbeg + p.kx < p.K) ? kbeg + p.kx : p.K;
+  return (kend > kbeg) ? (int)((kend - kbeg + KB - 1) / KB) : 0;
+}
+
+// One segment of a slot's work: the 128 x 128 tile (tm, tn) of X^T X over the stage window q0, q0 + S, ... (nstages of
+// them, all inside XCD x's K range), written to `out` (a 128 x 128 slab; zeros for an empty window).  `paced`: the
+// workgroup joins the XCD's pack for this segment.  All arguments are wave-uniform (SGPRs).
 template <bool KC, bool DIAG>
 __device__ __forceinline__ void gram_segment(const GramParams& p, double* smem, int x, int tm, int tn, int q0, int S,
-                                             double* out) {
+                                             int nstages, bool paced, int tid, double* out) {
   using P = Panel<BT, KC, GT>;
   double* sA0 = smem;
   double* sA1 = smem + P::LDS;
@@ -83,14 +101,10 @@ __device__ __forceinline__ void gram_segment(const GramParams& p, double* smem, 
 
   // opaque to the optimiser: nothing derived from the thread index is computed ahead of this point and kept alive (the
   // off-diagonal loop has no VGPR to spare: without the fence the column-major kernels spill 8 and 4 more bytes per lane)
-  int tid = threadIdx.x;
   asm volatile("" : "+v"(tid));
   const long m0 = (tm == p.tiles1 - 1) ? p.last0 : (long)tm * BT, n0 = (tn == p.tiles1 - 1) ? p.last0 : (long)tn * BT;
-  const long kend_x = ((long)x * p.kx + p.kx < p.K) ? (long)x * p.kx + p.kx : p.K;
-  const int nst_x = (kend_x > (long)x * p.kx) ? (int)((kend_x - (long)x * p.kx + KB - 1) / KB) : 0;
   const long kbeg = (long)x * p.kx;
-  const long kend = kend_x;
-  const int nstages = (nst_x > q0) ? (nst_x - q0 + S - 1) / S : 0;    // stages q0, q0+S, ...
+  const long kend = (kbeg + p.kx < p.K) ? kbeg + p.kx : p.K;
 
   const int lane = tid & 63, wid = tid >> 6;
   const int wm = wid >> 2, wn = wid & 3;
@@ -106,7 +120,7 @@ __device__ __forceinline__ void gram_segment(const GramParams& p, double* smem, 
   //   - more than PACE_DROP of its own stages BEHIND (started late: its CU was busy, or it is a second batch): it leaves
   //     the pack - takes its position and itself out of the word - and runs unpaced, so the pack never waits for it.
   // Workgroups that have not started are not in the word; finished ones stay in it and look like leaders.
-  unsigned long long* pace = p.pace ? p.pace + 16 * x : nullptr;
+  unsigned long long* pace = (p.pace && paced) ? p.pace + 16 * x : nullptr;
   int pacer = (pace && __builtin_amdgcn_readfirstlane(wid) == 0 && nstages > 0) ? 1 : 0;
   int pace_pos = 0, pace_cnt = 0;
   if (pacer && lane == 0) __hip_atomic_fetch_add(pace, PACE_ONE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -288,17 +302,51 @@ __device__ __forceinline__ void gram_check_xcd(const GramParams& p, int x) {
 }
 
 // Two launches (short snapshot sets, where the plan of the merged kernel does not apply): one tile kind per launch.
+// A regular slot runs one segment, a spare slot the tails of its tiles one after the other, each into that tile's tail
+// slab (the slab behind its regular ones).  Spare slots are elsewhere in K and never join the pack.
+// (The row-major diagonal kernel is held to the 80 VGPRs it always took: given 128, the scheduler spreads the LDS reads of
+// its stage loop over 92 and the launch measured 2.4 % slower, profiles/gram_spare_slots_ab.txt.)
 template <bool KC, bool DIAG>
-__global__ __launch_bounds__(GT, 4) void gram128_kernel(const GramParams p) {
+__global__ __launch_bounds__(GT, (DIAG && !KC) ? 6 : 4) void gram128_kernel(const GramParams p) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int x = blockIdx.x & 7, slot = blockIdx.x >> 3;
   gram_check_xcd(p, x);
   // (a byte table in the kernel arguments indexed by a run-time slot is fetched with VECTOR loads: without the
-  // readfirstlane every quantity derived from these four - tile origin, K range, panel pointers - lives in VGPRs and
+  // readfirstlane every quantity derived from these - tile origin, K range, panel pointers - lives in VGPRs and
   // all the "uniform" arithmetic of the loop is VALU work, which FP64 MFMAs cannot overlap with)
-  const int tm = __builtin_amdgcn_readfirstlane((int)p.slot_tm[slot]), tn = __builtin_amdgcn_readfirstlane((int)p.slot_tn[slot]),
-            q0 = __builtin_amdgcn_readfirstlane((int)p.slot_q[slot]), S = __builtin_amdgcn_readfirstlane((int)p.slot_S[slot]);
-  gram_segment<KC, DIAG>(p, smem, x, tm, tn, q0, S, p.slab + ((long)x * p.nslots + slot) * (BT * BT));
+  const int S = __builtin_amdgcn_readfirstlane((int)p.slot_S[slot]);
+  const int n_main = p.n_main[x];
+  // Both paths rebuild the thread index from the wave's number (an SGPR) and the lane's: the spare slots' loop must not
+  // carry threadIdx.x, a VGPR, through a segment, and the register allocation of the regular path then is the plain
+  // launch's (the workgroup is one-dimensional: wave w holds threads 64 w ... 64 w + 63 in lane order).
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (slot < p.n_regular) {
+    const int lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const int tm = __builtin_amdgcn_readfirstlane((int)p.slot_tm[slot]), tn = __builtin_amdgcn_readfirstlane((int)p.slot_tn[slot]),
+              q0 = __builtin_amdgcn_readfirstlane((int)p.slot_q[slot]), slab = __builtin_amdgcn_readfirstlane((int)p.slot_slab[slot]);
+    const int nstages = (n_main > q0) ? (n_main - q0 + S - 1) / S : 0;    // stages q0, q0+S, ... below n_main
+    gram_segment<KC, DIAG>(p, smem, x, tm, tn, q0, S, nstages, true, wave * 64 + lane, p.slab + ((long)x * p.nslots + slab) * (BT * BT));
+    return;
+  }
+  // A spare slot, in a loop of its own: the stage loops of the regular slots above stay the plain launch's.  Every
+  // iteration derives its state anew from the workgroup index behind a fence, so that nothing but the counter is carried
+  // through a segment (the off-diagonal stage loop has no register to spare for values hoisted out of this loop: one
+  // loop around a single call for both kinds of slot spilled 16 bytes per lane in the row-major kernel).
+#pragma unroll 1
+  for (int i = 0;; ++i) {
+    int wg = blockIdx.x, zero = 0;
+    asm volatile("" : "+s"(wg), "+s"(zero));
+    const int tid = wave * 64 + __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, zero));
+    const int xs = wg & 7, ss = wg >> 3;
+    const int Ss = __builtin_amdgcn_readfirstlane((int)p.slot_S[ss]);
+    if (i >= __builtin_amdgcn_readfirstlane((int)p.slot_tn[ss])) break;
+    const int r = (__builtin_amdgcn_readfirstlane((int)p.slot_tm[ss]) + i) * Ss;   // the first regular slot of the tile whose tail this is
+    const int tm = __builtin_amdgcn_readfirstlane((int)p.slot_tm[r]), tn = __builtin_amdgcn_readfirstlane((int)p.slot_tn[r]),
+              slab = __builtin_amdgcn_readfirstlane((int)p.slot_slab[r + Ss - 1]) + 1;
+    const int first = p.n_main[xs];
+    gram_segment<KC, DIAG>(p, smem, xs, tm, tn, first, 1, gram_range_stages(p, xs) - first, false, tid,
+                           p.slab + ((long)xs * p.nslots + slab) * (BT * BT));
+  }
 }
 
 // One launch: every slot runs the tile the plan gave it, off-diagonal or diagonal (gram_plan()).
@@ -312,10 +360,12 @@ __global__ __launch_bounds__(GT, 4) void gram128_merged_kernel(const GramParams 
   const int tm = __builtin_amdgcn_readfirstlane((int)g.tm[slot]), tn = __builtin_amdgcn_readfirstlane((int)g.tn[slot]),
             q0 = __builtin_amdgcn_readfirstlane((int)g.q[slot]), slab = __builtin_amdgcn_readfirstlane((int)g.slab[slot]);
   double* out = p.slab + ((long)x * p.nslots + slab) * (BT * BT);
+  const int nst_x = gram_range_stages(p, x);
+  const int nstages = (nst_x > q0) ? (nst_x - q0 + S - 1) / S : 0;    // stages q0, q0+S, ...
   if (tm == tn)
-    gram_segment<KC, true>(p, smem, x, tm, tn, q0, S, out);
+    gram_segment<KC, true>(p, smem, x, tm, tn, q0, S, nstages, true, threadIdx.x, out);
   else
-    gram_segment<KC, false>(p, smem, x, tm, tn, q0, S, out);
+    gram_segment<KC, false>(p, smem, x, tm, tn, q0, S, nstages, true, threadIdx.x, out);
 }
 
 struct GramReduceParams {
@@ -457,6 +507,70 @@ GramChoice gram_choose(int num_cus, long K, long n) {
   return c;
 }
 
+// Spare slots of one launch of the two-launch form: n_t tiles of one kind with s slots each leave R = slots_max - n_t s
+// slots of every XCD without a workgroup (the pipeline's 56 slots, 6 off-diagonal tiles: 9 each, 2 left over).  They take
+// the TAIL of every tile's range: regular slot (t, q) keeps its stages q, q + s, ... but only below n_main, and the stages
+// [n_main, end) of the tiles are dealt whole to the spare slots, at most m = ceil(n_t / R) tails each, which a spare slot
+// sweeps one after the other with stride 1.  A regular slot then does n_main / s stages and a spare one m (end - n_main):
+// equal at n_main = end m s / (1 + m s), taken per XCD (the last range is shorter).  Every tile gets one more slab per
+// XCD for its tail, behind its s regular ones.
+// Taken only when s is what the slots allow, not what `cap` allows (short sets keep the plain plan), and when the
+// spare workgroup with the fewest tails still sweeps the 48 stages that `cap` asks of a workgroup; spare slots beyond one
+// per tile stay unused.  Otherwise spare == 0 and the launch is the plain one: n_main is the whole range.
+int gram_n_main(int nst, int m, int s) {   // round(nst m s / (1 + m s))
+  const long ms = (long)m * s;
+  return (int)((2 * nst * ms + 1 + ms) / (2 * (1 + ms)));
+}
+struct GramSpare {
+  int spare, m;   // spare slots in use (0: the plain launch), most tails per spare slot
+};
+GramSpare gram_spare_plan(int slots_max, int n_t, int s, int cap, long kx) {
+  GramSpare sp{0, 0};
+  if (n_t < 1 || s < 1 || slots_max / n_t > cap) return sp;
+  const int R = std::min(slots_max - n_t * s, n_t);
+  if (R < 1) return sp;
+  const int m = (n_t + R - 1) / R;
+  const int nst = (int)(kx / KB);
+  if ((long)(n_t / R) * (nst - gram_n_main(nst, m, s)) < 48) return sp;
+  sp.spare = R; sp.m = m;
+  return sp;
+}
+
+// Fills one launch of the two-launch form for the tiles of one kind (`diag`), in upper-triangle order: the slot tables and
+// n_main of `p`, and the per-tile slab lists of the reduction (tile-major: s regular slabs, then the tail slab if the
+// launch has spare slots).  Returns the workgroups per XCD; *nslabs: the slabs per XCD.
+int gram_fill_launch(GramParams& p, int tiles1, bool diag, int s, const GramSpare& sp, unsigned char* first,
+                     unsigned char* count, int* nslabs) {
+  const int per_tile = s + (sp.spare ? 1 : 0);
+  int slot = 0, n_t = 0, t = 0;
+  for (int a = 0; a < tiles1; ++a)
+    for (int b = a; b < tiles1; ++b, ++t) {
+      if ((a == b) != diag) continue;
+      first[t] = (unsigned char)(n_t * per_tile); count[t] = (unsigned char)per_tile;
+      for (int q = 0; q < s; ++q, ++slot) {
+        p.slot_tm[slot] = (unsigned char)a; p.slot_tn[slot] = (unsigned char)b;
+        p.slot_q[slot] = (unsigned char)q; p.slot_S[slot] = (unsigned char)s;
+        p.slot_slab[slot] = (unsigned char)(n_t * per_tile + q);
+      }
+      ++n_t;
+    }
+  p.n_regular = slot;
+  for (int x = 0; x < 8; ++x) {
+    const long kbeg = (long)x * p.kx, kend = std::min(kbeg + p.kx, p.K);
+    const int nst_x = (kend > kbeg) ? (int)((kend - kbeg + KB - 1) / KB) : 0;
+    p.n_main[x] = sp.spare ? gram_n_main(nst_x, sp.m, s) : nst_x;
+  }
+  // spare slot j: the tails of tiles [t0, t0 + cnt), the first n_t % spare slots one tail more than the others
+  for (int j = 0, t0 = 0; j < sp.spare; ++j, ++slot) {
+    const int cnt = n_t / sp.spare + (j < n_t % sp.spare ? 1 : 0);
+    p.slot_tm[slot] = (unsigned char)t0; p.slot_tn[slot] = (unsigned char)cnt;
+    p.slot_q[slot] = 0; p.slot_S[slot] = (unsigned char)s; p.slot_slab[slot] = 0;
+    t0 += cnt;
+  }
+  *nslabs = n_t * per_tile;
+  return slot;
+}
+
 template <bool KC>
 int launch_gram_merged(rt_ctx* ctx, const GramParams& p, const GramSegs& g, int grid) {
   constexpr size_t lds = sizeof(double) * 4 * Panel<BT, KC, GT>::LDS;
@@ -508,11 +622,15 @@ int rt_gram128(rt_ctx* ctx, const double* X, int64_t ks, int64_t ms, int64_t K, 
   GramSegs g;
   GramReduceParams rp;
   int nslots_off, nslots_diag;   // slabs per XCD of the off-diagonal / diagonal tiles; one launch: one list for both
+  int wgs_off = 0, wgs_diag = 0; // two launches: workgroups per XCD of each (regular and spare slots)
+  GramParams p_diag = p;
   if (one_launch) {
     nslots_off = nslots_diag = gram_plan(tiles1, c.a, c.b, g, rp.first, rp.count);
   } else {
-    nslots_off = c.s_off * n_off;
-    nslots_diag = c.s_diag * tiles1;
+    const int cap = (int)(p.kx / KB / 48);
+    nslots_off = 0;
+    if (n_off) wgs_off = gram_fill_launch(p, tiles1, false, c.s_off, gram_spare_plan(c.slots, n_off, c.s_off, cap, p.kx), rp.first, rp.count, &nslots_off);
+    wgs_diag = gram_fill_launch(p_diag, tiles1, true, c.s_diag, gram_spare_plan(c.slots, tiles1, c.s_diag, cap, p.kx), rp.first, rp.count, &nslots_diag);
   }
   void* slab = nullptr;
   int rc = rt_scratch(ctx, sizeof(double) * BT * BT * 8 * (size_t)(one_launch ? nslots_off : nslots_off + nslots_diag), &slab);
@@ -530,40 +648,18 @@ int rt_gram128(rt_ctx* ctx, const double* X, int64_t ks, int64_t ms, int64_t K, 
   } else {
     // launch 1: off-diagonal tiles
     if (n_off) {
-      int slot = 0, t = 0;
-      for (int a = 0; a < tiles1; ++a)
-        for (int b = a; b < tiles1; ++b, ++t) {
-          if (a == b) continue;
-          rp.first[t] = (unsigned char)slot; rp.count[t] = (unsigned char)c.s_off;
-          for (int q = 0; q < c.s_off; ++q, ++slot) {
-            p.slot_tm[slot] = (unsigned char)a; p.slot_tn[slot] = (unsigned char)b;
-            p.slot_q[slot] = (unsigned char)q; p.slot_S[slot] = (unsigned char)c.s_off;
-          }
-        }
       p.slab = slab_off; p.nslots = nslots_off;
-      rc = kc ? launch_gram<true, false>(ctx, p, 8 * nslots_off) : launch_gram<false, false>(ctx, p, 8 * nslots_off);
+      rc = kc ? launch_gram<true, false>(ctx, p, 8 * wgs_off) : launch_gram<false, false>(ctx, p, 8 * wgs_off);
       if (rc != RT_OK) return rc;
     }
     // launch 2: diagonal tiles (upper MFMA tiles only)
-    {
-      int slot = 0, t = 0;
-      for (int a = 0; a < tiles1; ++a)
-        for (int b = a; b < tiles1; ++b, ++t) {
-          if (a != b) continue;
-          rp.first[t] = (unsigned char)slot; rp.count[t] = (unsigned char)c.s_diag;
-          for (int q = 0; q < c.s_diag; ++q, ++slot) {
-            p.slot_tm[slot] = (unsigned char)a; p.slot_tn[slot] = (unsigned char)a;
-            p.slot_q[slot] = (unsigned char)q; p.slot_S[slot] = (unsigned char)c.s_diag;
-          }
-        }
-      p.slab = slab_diag; p.nslots = nslots_diag;
-      p.pace = nullptr;   // every panel has one reader here
-      rc = kc ? launch_gram<true, true>(ctx, p, 8 * nslots_diag) : launch_gram<false, true>(ctx, p, 8 * nslots_diag);
-      if (rc != RT_OK) return rc;
-    }
+    p_diag.slab = slab_diag; p_diag.nslots = nslots_diag;
+    p_diag.pace = nullptr;   // every panel has one reader here
+    rc = kc ? launch_gram<true, true>(ctx, p_diag, 8 * wgs_diag) : launch_gram<false, true>(ctx, p_diag, 8 * wgs_diag);
+    if (rc != RT_OK) return rc;
   }
   RT_TRY(rt_profile_end(ctx, true));
-  ctx->last_grid = one_launch ? 8 * c.slots : 8 * (nslots_off + nslots_diag);
+  ctx->last_grid = one_launch ? 8 * c.slots : 8 * (wgs_off + wgs_diag);
   ctx->last_splits = 8 * (one_launch ? c.a : c.s_off);
   ctx->last_tile = 128 * 1000 + 128;
   const long total = n * n;
@@ -577,5 +673,26 @@ extern "C" int rt_gram_plan_info(int num_cus, int64_t n_rows, int64_t n_cols, in
   if (!out || num_cus < 8 || n_rows < 1 || n_cols < 1) return RT_ERR_ARG;
   const GramChoice c = gram_choose(num_cus, (long)n_rows, (long)n_cols);
   out[0] = c.form; out[1] = c.a; out[2] = c.b; out[3] = c.s_off; out[4] = c.s_diag;
+  return RT_OK;
+}
+
+// Diagnostic / test hook: the slot plan of one launch of the two-launch form for XCD xcd's row range (gram_spare_plan) -
+// out = {tiles, regular slots per tile, spare slots in use, most tails per spare slot, n_main, stages}.  No GPU needed.
+extern "C" int rt_gram_spare_plan_info(int num_cus, int64_t n_rows, int64_t n_cols, int launch, int xcd, int* out) {
+  if (!out || num_cus < 8 || n_rows < 1 || n_cols < 1 || launch < 0 || launch > 1 || xcd < 0 || xcd > 7) return RT_ERR_ARG;
+  const GramChoice c = gram_choose(num_cus, (long)n_rows, (long)n_cols);
+  const int tiles1 = (int)((n_cols + BT - 1) / BT), n_t = launch ? tiles1 : tiles1 * (tiles1 - 1) / 2;
+  if (c.form != 1 || n_t < 1) return RT_ERR_UNSUPPORTED;
+  GramParams p;
+  p.K = (long)n_rows;
+  p.kx = ((p.K + 7) / 8 + KB - 1) / KB * KB;
+  const int s = launch ? c.s_diag : c.s_off;
+  const GramSpare sp = gram_spare_plan(c.slots, n_t, s, (int)(p.kx / KB / 48), p.kx);
+  unsigned char first[MAX_TILES], count[MAX_TILES];
+  int nslabs;
+  gram_fill_launch(p, tiles1, launch == 1, s, sp, first, count, &nslabs);
+  const long kbeg = (long)xcd * p.kx, kend = std::min(kbeg + p.kx, p.K);
+  out[0] = n_t; out[1] = s; out[2] = sp.spare; out[3] = sp.m; out[4] = p.n_main[xcd];
+  out[5] = (kend > kbeg) ? (int)((kend - kbeg + KB - 1) / KB) : 0;
   return RT_OK;
 }
