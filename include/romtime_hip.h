@@ -420,6 +420,36 @@ int rt_p1_local_assembly(rt_ctx* ctx, int kind, int64_t nx, const int64_t* rows,
                          int64_t n_states, const double* h, const double* coef, int state_mode, const double* state,
                          double* out);
 
+/* ---- snapshot sets of the closed-form 1-D P1 operators over a product grid (what the six (M)DEIM objects are trained on,
+ *      rom/hrom.py:419-448, 1092-1146: one whole operator per (mu, t), deim/deim.py:384-389, or per (mu, t, psi),
+ *      deim/nonlinear.py:437-443), since version 440 ----
+ * out is (n_par n_fun) x m: column (p, f) - parameter row p, nodal function f - is the m contiguous values at
+ * out + (p n_fun + f) m, so out is the RT_COL_MAJOR m x S set, S = n_par n_fun, that rt_gram and rt_pod_orth take as it is.
+ *   value = beta out_old + (zero_first && e == 0 ? 0 : v),
+ * v bit for bit what rt_p1_local_assembly returns for the same kind, entry (rows[e], cols[e]), h, coef and nodal function
+ * (both call one function, csrc/p1_entry.h).  Parameter row p carries h[p], coef[p] (NULL = 1) and, by par_mode, what
+ * rt_p1_local_assembly's state_mode carries: 2 = par is n_par ramp amplitudes, 3 = par is n_par x 3 polynomial
+ * coefficients (RT_P1_LOAD_P2 only), 0 = par is NULL.  fun: n_fun x (nx + 1) nodal functions shared by every parameter row
+ * (n_fun x (2 nx + 1) for RT_P1_LOAD_P2).  Exactly one of par / fun supplies the nodal function of the kinds that integrate
+ * one (RT_P1_TRILINEAR and the loads; with par, n_fun = 1); the other kinds take n_fun = 1, fun = NULL, par = NULL.
+ *   - beta = 0 does not read out; otherwise v is rounded before it is added to the rounded beta out_old (beta = 1: the
+ *     sum of two tables, rounded once per entry, without a temporary).  zero_first: entry 0 of every column adds 0 (the
+ *     boundary entry of the MDEIM snapshots, deim/deim.py:388-389).
+ *   - One launch for any n_par n_fun m < 2^62: a grid stride over (column, entry), lanes along the entries.  Vector stores
+ *     only, no atomics, every word of out written by one thread.  A row outside [0, nx] gives 0.
+ *   - Null rows, h, out (cols for the matrix kinds), sizes < 1, nx < 2, an unknown kind or par_mode, a par / fun combination
+ *     the kind cannot take and a count of 2^62 or more return RT_ERR_ARG, nx > 2^22 RT_ERR_UNSUPPORTED, all before any launch.
+ *   - rt_last_launch_info: [0] workgroups, [1] launches (1), [2] 1 x 256 words per workgroup and pass. */
+int rt_p1_snapshot_sets(rt_ctx* ctx, int kind, int64_t nx, const int64_t* rows, const int64_t* cols, int64_t m,
+                        int64_t n_par, const double* h, const double* coef, int par_mode, const double* par,
+                        int64_t n_fun, const double* fun, int zero_first, double beta, double* out);
+/* The argument checks and the launch plan of rt_p1_snapshot_sets for a ctx of num_cus CUs - host logic only, no GPU and no
+ * pointer is followed: the same return code, and on RT_OK info2 (may be NULL) = {workgroups, launches}. */
+int rt_p1_snapshot_sets_plan_info(int num_cus, int kind, int64_t nx, const int64_t* rows, const int64_t* cols, int64_t m,
+                                  int64_t n_par, const double* h, const double* coef, int par_mode, const double* par,
+                                  int64_t n_fun, const double* fun, int zero_first, double beta, const double* out,
+                                  int64_t* info2);
+
 /* ---- full-order BDF sweeps of the closed-form 1-D P1 models (the time loop of OneDimensionalSolver.solve,
  *      fom/base.py:693-831, for the heat problem fom/heat.py:57-82, 251-262 and the piston fom/nonlinear.py:322-494;
  *      testing/mock.py: MockHeatEquation.solve, MockBurgers.solve) for a batch of parameter points, since version 390 ---- */

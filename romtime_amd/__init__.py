@@ -5,7 +5,7 @@ src/romtime/deim/__init__.py:1-9); the numerics run in hand-written HIP kernels 
 of ``include/romtime_hip.h``.  There is no CPU fallback: without the built library and a GPU the
 hot-path calls raise ``RomtimeHipError``.
 """
-from . import fom, interpolation, online, outputs
+from . import collect, fom, interpolation, online, outputs
 from ._lib import RomtimeHipError
 from .base import Reductor
 from .deim import DiscreteEmpiricalInterpolation
@@ -46,6 +46,7 @@ __all__ = [
     "RomtimeHipError",
     "outputs",
     "interpolation",
+    "collect",
     "fom",
     "online",
     "shutdown",

@@ -82,6 +82,9 @@ SIGNATURES = {
     "rt_interpolation_errors_plan_info": (_int, [_int, _p, _i64, C.POINTER(_i64), _i64, _p, _i64, _int, _i64, _i64, _i64, _i64,
                                                  C.c_double, _p, _p, C.POINTER(_i64)]),
     "rt_p1_local_assembly": (_int, [_p, _int, _i64, _p, _p, _i64, _i64, _p, _p, _int, _p, _p]),
+    "rt_p1_snapshot_sets": (_int, [_p, _int, _i64, _p, _p, _i64, _i64, _p, _p, _int, _p, _i64, _p, _int, C.c_double, _p]),
+    "rt_p1_snapshot_sets_plan_info": (_int, [_int, _int, _i64, _p, _p, _i64, _i64, _p, _p, _int, _p, _i64, _p, _int, C.c_double, _p,
+                                             C.POINTER(_i64)]),
     "rt_p1_fom_bdf_sweep": (_int, [_p, _p, _p, _i64, _i64, _p]),
     "rt_p1_fom_bdf_sweep_plan_info": (_int, [_int, _p, _i64, _i64, C.POINTER(_i64)]),
     "rt_p1_fom_bdf_sweep_certified": (_int, [_p, _p, _p, _i64, _i64, C.c_double, _p, _p]),

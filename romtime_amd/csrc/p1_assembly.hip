@@ -27,6 +27,7 @@
 // polynomial  a0 + a1 x + a2 x^2  in the physical coordinate x = node h (three coefficients per state).  For load_p2
 // the nodal function has 2 nx + 1 values per state: vertex k at 2k, midpoint of cell k at 2k + 1.
 #include "common.h"
+#include "p1_entry.h"
 
 namespace {
 
@@ -41,47 +42,14 @@ struct P1Params {
   double* out;            // n_states x m
 };
 
-__device__ __forceinline__ double nodal(const P1Params& p, long s, long k) {
-  if (p.state_mode == 1) return p.state[s * (p.nx + 1) + k];
-  return p.state[s] * ((double)k / (double)p.nx);
-}
-
-// load_p2: value k of the P2 function of state s (k = 2 * vertex, odd k = cell midpoints; x = k h / 2)
-__device__ __forceinline__ double nodal_p2(const P1Params& p, long s, long k, double h) {
-  if (p.state_mode == 1) return p.state[s * (2 * p.nx + 1) + k];
-  const double x = 0.5 * h * (double)k;
-  const double* a = p.state + 3 * s;
-  return fma(fma(a[2], x, a[1]), x, a[0]);
-}
-
 __global__ void p1_local_assembly_kernel(const P1Params p) {
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long s = blockIdx.y;
   if (e >= p.m) return;
   const long i = p.rows[e], j = p.cols ? p.cols[e] : i;
-  const bool dirichlet = (i == 0) || (i == p.nx);
   const double h = p.h[s], c = p.coef ? p.coef[s] : 1.0;
-  const long d = j - i;
-  double v = 0.0;
-  if (p.kind == RT_P1_LOAD) {
-    if (!dirichlet) v = c * h / 6.0 * (nodal(p, s, i - 1) + 4.0 * nodal(p, s, i) + nodal(p, s, i + 1));
-  } else if (p.kind == RT_P1_LOAD_P2) {
-    if (!dirichlet) v = c * h / 3.0 * (nodal_p2(p, s, 2 * i - 1, h) + nodal_p2(p, s, 2 * i, h) + nodal_p2(p, s, 2 * i + 1, h));
-  } else if (dirichlet) {
-    v = (d == 0) ? 1.0 : 0.0;
-  } else if (d >= -1 && d <= 1) {
-    switch (p.kind) {
-      case RT_P1_MASS: v = c * h * (d == 0 ? 4.0 / 6.0 : 1.0 / 6.0); break;
-      case RT_P1_STIFFNESS: v = c / h * (d == 0 ? 2.0 : -1.0); break;
-      case RT_P1_CONVECTION: v = c * (d == 0 ? 0.0 : (d == 1 ? -0.5 : 0.5)); break;
-      default: {  // RT_P1_TRILINEAR
-        const double wm = nodal(p, s, i - 1), w0 = nodal(p, s, i), wp = nodal(p, s, i + 1);
-        const double b_prev = (wm + 2.0 * w0) / 6.0, a_here = (2.0 * w0 + wp) / 6.0;
-        v = c * (d == -1 ? -b_prev : (d == 0 ? b_prev - a_here : a_here));
-      }
-    }
-  }
-  p.out[s * p.m + e] = v;
+  const P1Nodal f{p.state_mode, p.nx, p.state ? p.state + s * p1_nodal_width(p.kind, p.state_mode, p.nx) : nullptr};
+  p.out[s * p.m + e] = p1_entry_value(p.kind, p.nx, i, j, h, c, f);   // the entry formulas: p1_entry.h
 }
 
 }  // namespace
@@ -104,7 +72,7 @@ extern "C" int rt_p1_local_assembly(rt_ctx* ctx, int kind, int64_t nx, const int
     const long ns = (n_states - s0 < 65535) ? n_states - s0 : 65535;
     q.h = h + s0;
     q.coef = coef ? coef + s0 : nullptr;
-    const long per_state = state_mode == 1 ? (kind == RT_P1_LOAD_P2 ? 2 * nx + 1 : nx + 1) : (state_mode == 3 ? 3 : 1);
+    const long per_state = p1_nodal_width(kind, state_mode, (long)nx);
     q.state = state ? state + s0 * per_state : nullptr;
     q.out = out + s0 * m;
     q.n_states = ns;

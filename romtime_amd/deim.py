@@ -64,6 +64,11 @@ class DiscreteEmpiricalInterpolation(Reductor):
     # expansion each).  "device": ``interpolation.evaluate`` - the snapshots of a parameter point certified by one kernel
     # call (rt_interpolation_errors); its errors differ from the host loop's by rounding, so the caller chooses.
     EVALUATE_ON = "host"
+    # Where the snapshot sets of the offline walk (and the exact snapshots of the device ``evaluate``) come from.  "host":
+    # one FOM callback per sample, stacked and uploaded.  "device": ``collect`` - for a FOM with ``p1_closed_form`` the
+    # whole set of a parameter point in one launch (rt_p1_snapshot_sets), no callback; NotImplementedError where the
+    # callback has no closed form.  The sets differ from the callbacks' by rounding, so the caller chooses.
+    SNAPSHOTS_ON = "host"
 
     def __init__(self, assemble, grid=None, tree_walk_params=None, name=None) -> None:
         super().__init__(grid=grid)
@@ -109,14 +114,20 @@ class DiscreteEmpiricalInterpolation(Reductor):
             value = getattr(self, attr)
             if value is not None:
                 setattr(new, attr, deepcopy(value))
-        if "EVALUATE_ON" in self.__dict__:
-            new.EVALUATE_ON = self.EVALUATE_ON
+        for attr in ("EVALUATE_ON", "SNAPSHOTS_ON", "closed_form"):      # instance overrides travel
+            if attr in self.__dict__:
+                setattr(new, attr, self.__dict__[attr])
         return new
 
     def _evaluate_on_device(self):
         if self.EVALUATE_ON not in ("host", "device"):
             raise ValueError(f"EVALUATE_ON must be 'host' or 'device', not {self.EVALUATE_ON!r}")
         return self.EVALUATE_ON == "device"
+
+    def _snapshots_on_device(self):
+        if self.SNAPSHOTS_ON not in ("host", "device"):
+            raise ValueError(f"SNAPSHOTS_ON must be 'host' or 'device', not {self.SNAPSHOTS_ON!r}")
+        return self.SNAPSHOTS_ON == "device"
 
     # ---- device residency of the (large) bases -----------------------------------------
     def _device(self, key, array):
@@ -180,19 +191,30 @@ class DiscreteEmpiricalInterpolation(Reductor):
         The time-level PODs are a sequence of independent small PODs: every parameter's snapshot set is assembled by
         the FOM callback on the host, uploaded once and run through the device's POD lanes (``walks.pod_sequence``);
         the per-parameter bases stay on the device, where they are concatenated for the mu-level POD.  Only the final
-        basis and the spectra of the report come back.  A subclass that overrides ``walk_time`` keeps the plain loop."""
+        basis and the spectra of the report come back.  A subclass that overrides ``walk_time`` keeps the plain loop.
+        With ``SNAPSHOTS_ON = "device"`` the sets are built on the device instead (``collect.time_level_set``): same
+        parameter points, same bookkeeping, no FOM callback."""
         from . import walks
 
+        on_device = self._snapshots_on_device()                      # a wrong value: before any bookkeeping
         space = mu_space if mu_space else self.build_sampling_space(num=num_snapshots, rnd=self.random_state)
         off = self.report[Stage.OFFLINE]
         if type(self).walk_time is not DiscreteEmpiricalInterpolation.walk_time:
             return self._tree_walk_host(space, ts, normalize, num_mu, num_t, tol_mu, tol_t)
         indices = []
+        if on_device:
+            from . import collect
+
+            space = list(space)                                      # drawn once, as the loop below would draw it
+            resolved = collect.resolve(self, space, ts)              # no closed form: before any bookkeeping
 
         def time_level_sets():
             for mu in space:
                 mu_idx, mu = self.add_mu(step=Stage.OFFLINE, mu=mu)
                 indices.append(mu_idx)
+                if on_device:
+                    yield collect.time_level_set(self, mu, ts, resolved=resolved)
+                    continue
                 yield walks.upload_columns([self.assemble_snapshot(mu, t) for t in ts],
                                            zero_first_row=self.TYPE == EmpiricalInterpolation.MDEIM)   # deim.py:384-389
 

@@ -21,7 +21,8 @@ from .conventions import EmpiricalInterpolation, Stage
 
 MAX_M = 128                      # rt_interpolation_errors and rt_dense_solve_multi: the factors and a stage fit the LDS
 MAX_COLUMNS = 4096               # snapshots per kernel call unless the caller says otherwise
-CLOSED_FORM_KINDS = ("mass", "stiffness", "convection", "nonlinear_lifting", "lifting")
+CLOSED_FORM_KINDS = ("mass", "stiffness", "convection", "nonlinear_lifting", "lifting", "trilinear", "forcing", "rhs")
+COLLECT_KINDS = ("trilinear", "forcing", "rhs")      # through ``collect.assemble`` (rt_p1_snapshot_sets)
 
 
 def fold(reductor) -> torch.Tensor:
@@ -93,10 +94,12 @@ def evaluate(reductor, ts, num=None, mu_space=None, funcs=None, max_columns=MAX_
     ``len(ts)`` errors - and one FOM callback per sample: the exact snapshots of a parameter point are stacked on the
     device (``walks.upload_columns``) and certified by one kernel call per chunk of at most ``max_columns`` columns.
     N-MDEIM: the columns run over (t, psi), the error of a time instant is the mean over the states ``funcs`` (default
-    the reductor's ``u_n``), and a chunk holds whole time instants."""
+    the reductor's ``u_n``), and a chunk holds whole time instants.  A reductor with ``SNAPSHOTS_ON = "device"`` takes
+    its exact snapshots from ``collect`` (one launch per chunk) instead: no FOM callback at all."""
     from . import walks
 
     ts = list(ts)
+    on_device = reductor._snapshots_on_device()
     nonlinear = reductor.TYPE == EmpiricalInterpolation.NONLINEAR
     if nonlinear:
         u_n = reductor.u_n if funcs is None else funcs
@@ -105,10 +108,21 @@ def evaluate(reductor, ts, num=None, mu_space=None, funcs=None, max_columns=MAX_
         n_psi = 1
     per_chunk = max(int(max_columns) // n_psi, 1) if np.isfinite(max_columns) else max(len(ts), 1)   # time instants
     fold(reductor)                                       # a singular PT_U or too many entries: before any bookkeeping
-    for mu in _space(reductor, num, mu_space):
+    space = _space(reductor, num, mu_space)
+    if on_device:
+        from . import collect
+
+        space = list(space)
+        resolved = collect.resolve(reductor, space, ts)  # no closed form: before any bookkeeping
+    for mu in space:
         mu_idx, mu = reductor.add_mu(step=Stage.ONLINE, mu=mu)
         errors = list(reductor.errors_rom[mu_idx])
         for lo in range(0, len(ts), per_chunk):
+            if on_device:
+                F = collect.exact_snapshots(reductor, mu, ts[lo:lo + per_chunk], funcs=u_n if nonlinear else None,
+                                            resolved=resolved)
+                errors.extend(snapshot_errors(reductor, F, group=n_psi))
+                continue
             if nonlinear:
                 columns = [reductor.assemble_snapshot(mu=mu, t=t, u_n=u_n[:, i]) for t in ts[lo:lo + per_chunk]
                            for i in range(n_psi)]
@@ -118,29 +132,47 @@ def evaluate(reductor, ts, num=None, mu_space=None, funcs=None, max_columns=MAX_
         reductor.errors_rom[mu_idx] = np.array(errors)
 
 
-def evaluate_closed_form(reductor, kind, fom, mus, ts, max_columns=MAX_COLUMNS) -> np.ndarray:
+def evaluate_closed_form(reductor, kind, fom, mus, ts, max_columns=MAX_COLUMNS, funcs=None) -> np.ndarray:
     """Interpolation errors at every ``(mu, t)`` for a FOM with ``p1_closed_form`` (the counterpart of
     ``sweep.hrom_terms_on_device``): the exact snapshots are built on the device by ``ops.p1_local_assembly`` over the
     reductor's whole topology, in chunks of (t, mu) states, and never exist on the host.  ``kind``: "mass",
     "stiffness", "convection", "nonlinear_lifting" (the trilinear form with the lifting ramp) or "lifting" (the load
-    vector of the lifting's time derivative).  No FOM callback.  Returns (n_mu, len(ts))."""
+    vector of the lifting's time derivative); through the kind rules of ``collect.assemble``: "trilinear" (the
+    state-dependent operator of the states ``funcs``, N_h x N_psi; the error of a (mu, t) is the mean over the states, as
+    N-MDEIM's ``evaluate`` forms it), "forcing" and "rhs" (the load vectors of a DEIM reductor).  No FOM callback.
+    Returns (n_mu, len(ts))."""
     if kind not in CLOSED_FORM_KINDS:
         raise ValueError(f"kind must be one of {CLOSED_FORM_KINDS}, not {kind!r}")
+    if kind == "trilinear" and funcs is None:
+        raise ValueError("kind 'trilinear' needs the states: funcs=(N_h x N_psi)")
     if not hasattr(fom, "p1_closed_form"):
         raise NotImplementedError("the FOM does not expose closed-form P1 scalars (p1_closed_form)")
     mus, ts = list(mus), np.asarray(ts, dtype=float)
     cf = fom.p1_closed_form(mus, ts)
     nx, n_mu, nt = int(cf["nx"]), len(mus), ts.size
-    if kind == "lifting":
+    if kind in ("lifting", "forcing", "rhs"):
         rows, cols = ops.to_device_index(np.arange(nx + 1)), None
     else:
         rows, cols = ops.to_device_index(reductor.rows), ops.to_device_index(reductor.cols)
     Psi, idx, pin = fold(reductor), flat_indices(reductor), pin_of(reductor)
     flat = lambda a, lo, hi: np.ascontiguousarray(np.asarray(a, dtype=np.float64)[lo:hi]).reshape(-1)
-    per_chunk = max(int(max_columns) // n_mu, 1) if np.isfinite(max_columns) else nt
+    n_psi = 1
+    if kind == "trilinear":
+        from . import collect
+
+        fun = collect._functions(reductor, funcs)
+        n_psi = int(fun.shape[0])
+    per_chunk = max(int(max_columns) // (n_mu * n_psi), 1) if np.isfinite(max_columns) else nt
     out = np.empty((nt, n_mu))
     for lo in range(0, nt, per_chunk):
         hi = min(lo + per_chunk, nt)
+        if kind in COLLECT_KINDS:
+            from . import collect
+
+            table = collect.assemble(kind, cf, rows, cols, fun=fun if kind == "trilinear" else None, lo=lo, hi=hi)
+            err = ops.interpolation_errors(Psi, idx, table.T, group=n_psi, pin=pin)
+            out[lo:hi] = err.cpu().numpy().reshape(hi - lo, n_mu)
+            continue
         h = flat(cf["h"], lo, hi)
         if kind == "mass":
             table = ops.p1_local_assembly("mass", nx, rows, cols, h)

@@ -82,9 +82,15 @@ class MatrixDiscreteEmpiricalInterpolationNonlinear(MatrixDiscreteEmpiricalInter
         and the per-parameter results again for the mu level (``walks``)."""
         from . import walks
 
+        on_device = self._snapshots_on_device()                      # a wrong value: before any bookkeeping
         space = mu_space if mu_space else self.build_sampling_space(num=num_snapshots, rnd=self.random_state)
         off = self.report[Stage.OFFLINE]
         per_mu = []
+        if on_device:
+            from . import collect
+
+            space = list(space)                                      # drawn once, as the loop below would draw it
+            collect.resolve(self, space, ts)                         # no closed form: before any bookkeeping
         for mu in space:
             mu_idx, mu = self.add_mu(step=Stage.OFFLINE, mu=mu)
             out = self._walk_time_device(mu=mu, ts=ts, num_t=num_t, tol_t=tol_t, normalize=normalize)
@@ -105,6 +111,12 @@ class MatrixDiscreteEmpiricalInterpolationNonlinear(MatrixDiscreteEmpiricalInter
         from . import walks
 
         u_n = self.u_n
+        if self._snapshots_on_device():
+            from . import collect
+
+            sets = collect.state_level_sets(self, mu, ts, u_n)       # one launch for the point, no FOM callback
+            per_t = [out["Q"] for out in walks.pod_sequence(sets, num=num_t, tol=tol_t, normalize=normalize)]
+            return walks.pod_of_stack(per_t, num=num_t, tol=tol_t, normalize=normalize)
 
         def basis_level_sets():
             for t in ts:

@@ -494,6 +494,55 @@ def p1_local_assembly(kind: str, nx: int, rows, cols, h, coef=None, state=None, 
     return out
 
 
+def p1_snapshot_sets(kind: str, nx: int, rows, cols, h, coef=None, ramp=None, poly=None, fun=None, zero_first: bool = False,
+                     out: torch.Tensor = None, beta: float = 0.0) -> torch.Tensor:
+    """Closed-form 1-D P1 operator values over a product grid: the (n_par * n_fun, m) table whose row ``p * n_fun + f`` is
+    the operator of parameter row p - ``h`` (n_par) cell sizes, ``coef`` (n_par) optional factors, ``ramp`` (n_par)
+    amplitudes or ``poly`` (n_par, 3) coefficients as in ``p1_local_assembly`` - and nodal function f of ``fun`` (n_fun,
+    nx + 1; (n_fun, 2 nx + 1) for ``load_p2``), shared by every parameter row.  Exactly one of ``ramp`` / ``poly`` / ``fun``
+    for the trilinear and load kinds, none for the others.  Its ``.T`` is the column-major m x S snapshot set the POD
+    takes; values are bit for bit those of ``p1_local_assembly``.  ``zero_first``: entry 0 of every column is 0 (the MDEIM
+    convention).  ``out``, ``beta``: the result is ``beta * out + table`` written into ``out`` (beta = 0 does not read it).
+    rt_p1_snapshot_sets."""
+    ctx = Context.current()
+    rows = rows if isinstance(rows, torch.Tensor) else to_device_index(rows)
+    cols = None if cols is None else (cols if isinstance(cols, torch.Tensor) else to_device_index(cols))
+    h = to_device(np.atleast_1d(h) if not isinstance(h, torch.Tensor) else h).contiguous().reshape(-1)
+    n_par, m = h.numel(), rows.numel()
+    coef = None if coef is None else to_device(np.atleast_1d(coef) if not isinstance(coef, torch.Tensor) else coef).contiguous()
+    if coef is not None and coef.numel() != n_par:
+        raise RomtimeHipError("p1_snapshot_sets: `coef` must have one value per parameter row")
+    mode, par, n_fun, fn = 0, None, 1, None
+    if ramp is not None:
+        par = to_device(np.atleast_1d(ramp) if not isinstance(ramp, torch.Tensor) else ramp).contiguous()
+        if par.numel() != n_par:
+            raise RomtimeHipError("p1_snapshot_sets: `ramp` must have one amplitude per parameter row")
+        mode = 2
+    if poly is not None:
+        if par is not None:
+            raise RomtimeHipError("p1_snapshot_sets: `ramp` and `poly` exclude each other")
+        par = to_device(poly).contiguous()
+        if tuple(par.shape) != (n_par, 3):
+            raise RomtimeHipError("p1_snapshot_sets: `poly` must be (n_par, 3)")
+        mode = 3
+    if fun is not None:
+        fn = to_device(fun).contiguous()
+        width = 2 * nx + 1 if kind == "load_p2" else nx + 1
+        if fn.dim() != 2 or fn.shape[1] != width or fn.shape[0] < 1:
+            raise RomtimeHipError(f"p1_snapshot_sets: `fun` must be (n_fun, {width}) for kind {kind!r}")
+        n_fun = int(fn.shape[0])
+    if out is None:
+        if beta != 0.0:
+            raise RomtimeHipError("p1_snapshot_sets: beta != 0 needs `out`")
+        out = torch.empty((n_par * n_fun, m), dtype=torch.float64, device=h.device)
+    elif tuple(out.shape) != (n_par * n_fun, m) or out.dtype != torch.float64 or not out.is_contiguous():
+        raise RomtimeHipError(f"p1_snapshot_sets: `out` must be a contiguous float64 ({n_par * n_fun}, {m}) tensor")
+    ctx.check(ctx.lib.rt_p1_snapshot_sets(ctx.handle, P1_KINDS[kind], int(nx), _ptr(rows), _ptr(cols), m, n_par, _ptr(h), _ptr(coef),
+                                          mode, _ptr(par), n_fun, _ptr(fn), int(bool(zero_first)), float(beta), _ptr(out)),
+              "rt_p1_snapshot_sets")
+    return out
+
+
 def p1_fom_plan(nx: int, n_mu: int = 1, nt: int = 1, num_cus: int = 256):
     """(workgroups, partitions per system, rows per partition) of ``p1_fom_bdf_sweep`` for nx cells - host logic only,
     no GPU (rt_p1_fom_bdf_sweep_plan_info); raises where the sweep would refuse the sizes."""

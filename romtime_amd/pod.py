@@ -295,7 +295,7 @@ class _SmallEig:
         H, S = 0.5 * (HS[:k] + HS[:k].T), 0.5 * (HS[k:] + HS[k:].T)
         with _blas_threads(1):  # k x k: threads only burn the CPU quota
             theta, C = small_eigh(H, S, check_finite=False)
-        theta, C = theta[::-1], np.ascontiguousarray(C[:, ::-1])
+        theta, C = theta[::-1], np.array(C[:, ::-1], order="C")   # a copy: the reversed view of a 1 x 1 counts as contiguous
         if np.abs(theta - lam[:k]).max() > 1e-9 * max(lam[0], 1e-300):
             raise _lib.RomtimeHipError("device eigenvectors failed the Rayleigh-Ritz cross-check")
         return ops.gemm_nn(Z, ops.to_device(C, Z.device))
