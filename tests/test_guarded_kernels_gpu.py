@@ -167,8 +167,8 @@ GEMM_TN_CASES = [
 ]
 
 
-@pytest.mark.parametrize("case", GEMM_TN_CASES, ids=[c[0] for c in GEMM_TN_CASES])
-def test_gemm_tn_guarded(ctx, cus, case):
+def _gemm_tn_case(ctx, cus, case):
+    """The body of test_gemm_tn_guarded on a ctx that sizes its grids for ``cus`` CUs; returns C."""
     _, N, m, n, la, lb, pa, pb, mis, pc, sym = case
     rng = np.random.default_rng(N + m + n)
     b = _bits_for(N)
@@ -188,8 +188,15 @@ def test_gemm_tn_guarded(ctx, cus, case):
     assert ctx.launch_info() == want
     assert (skinny is not None) == case[0].startswith("skinny")
     assert (want["splits"] == 1) == (case[0] == "generic_no_split")
-    _exact(_host(Cm.t), A.T @ B)
+    got = _host(Cm.t)
+    _exact(got, A.T @ B)
     _clean([Cm], [(Ad, A)] + ([] if sym else [(Bd, B)]))
+    return got
+
+
+@pytest.mark.parametrize("case", GEMM_TN_CASES, ids=[c[0] for c in GEMM_TN_CASES])
+def test_gemm_tn_guarded(ctx, cus, case):
+    _gemm_tn_case(ctx, cus, case)
 
 
 # ---- rt_gemm_nn_axpby ------------------------------------------------------------------------------------------------
@@ -206,8 +213,8 @@ GEMM_NN_CASES = [
 ]
 
 
-@pytest.mark.parametrize("case", GEMM_NN_CASES, ids=[c[0] for c in GEMM_NN_CASES])
-def test_gemm_nn_axpby_guarded(ctx, cus, case):
+def _gemm_nn_case(ctx, cus, case):
+    """The body of test_gemm_nn_axpby_guarded on a ctx that sizes its grids for ``cus`` CUs; returns Y."""
     _, N, n, k, lx, px, mis, pt, ly, py, alpha, beta, route = case
     rng = np.random.default_rng(N + n + k)
     b = _bits_for(2 * n + 2)
@@ -230,8 +237,15 @@ def test_gemm_nn_axpby_guarded(ctx, cus, case):
     else:
         assert info == gd.gemm_plan(N, k, n, False, False, cus)
     ref = alpha * (X @ T) + (beta * Y0 if beta != 0.0 else 0.0)
-    _exact(_host(Y.t), ref)
+    got = _host(Y.t)
+    _exact(got, ref)
     _clean([Y], [(Xd, X), (Td, T)])
+    return got
+
+
+@pytest.mark.parametrize("case", GEMM_NN_CASES, ids=[c[0] for c in GEMM_NN_CASES])
+def test_gemm_nn_axpby_guarded(ctx, cus, case):
+    _gemm_nn_case(ctx, cus, case)
 
 
 # ---- rt_rank_update ----------------------------------------------------------------------------------------------------
@@ -246,8 +260,8 @@ RANK_UPDATE_CASES = [
 ]
 
 
-@pytest.mark.parametrize("case", RANK_UPDATE_CASES, ids=[c[0] for c in RANK_UPDATE_CASES])
-def test_rank_update_guarded(ctx, cus, case):
+def _rank_update_case(ctx, cus, case):
+    """The body of test_rank_update_guarded on a ctx that sizes its grids for ``cus`` CUs; returns the updated matrix."""
     _, N, n, k, use_cs, ps, pd, ms, md, in_place, alpha = case
     rng = np.random.default_rng(N + n + k)
     g, f = gd.graded_exponents(rng, N, 60), gd.graded_exponents(rng, n, 60)
@@ -268,12 +282,19 @@ def test_rank_update_guarded(ctx, cus, case):
     ctx.check(ctx.lib.rt_rank_update(ctx.handle, P(Ysd), Ysd.stride(0), P(csd), P(Xd), Xd.stride(0), P(Td), Td.stride(0),
                                      N, k, n, alpha, P(dst), ldd), "rt_rank_update")
     assert ctx.launch_info() == gd.rank_update_plan(N, n, cus)
-    _exact(_host(dst), ref)
+    got = _host(dst)
+    _exact(got, ref)
     ops = [(Xd, X), (Td, T)] + ([(csd, cs[None, :])] if use_cs else [])
     if in_place:
         _clean([], ops + [(Ysd, ref)])          # the poison around the updated matrix is untouched
     else:
         _clean([Yd], ops + [(Ysd, Ys)])
+    return got
+
+
+@pytest.mark.parametrize("case", RANK_UPDATE_CASES, ids=[c[0] for c in RANK_UPDATE_CASES])
+def test_rank_update_guarded(ctx, cus, case):
+    _rank_update_case(ctx, cus, case)
 
 
 # ---- rt_transpose ------------------------------------------------------------------------------------------------------
@@ -304,9 +325,12 @@ def _csr(rng, N, ncols, per_row=6, empty_every=7):
     return np.array(indptr, dtype=np.int64), np.array(indices, dtype=np.int64)
 
 
-@pytest.mark.parametrize("r,pv,py,mis", [(7, 1, 2, True), (64, 0, 3, False), (130, 5, 1, False)])
-def test_csr_spmm_guarded(ctx, r, pv, py, mis):
-    N, ncols = 500, 300
+CSR_SPMM_CASES = [(7, 1, 2, True), (64, 0, 3, False), (130, 5, 1, False)]       # r, V ld_pad, Y ld_pad, V misaligned
+
+
+def _csr_spmm_case(ctx, r, pv, py, mis, N=500):
+    """The body of test_csr_spmm_guarded for N rows; returns Y."""
+    ncols = 300
     rng = np.random.default_rng(r)
     indptr, indices = _csr(rng, N, ncols)
     data = exact_operands(rng, (1, len(indices)), 10)[0]
@@ -317,8 +341,15 @@ def test_csr_spmm_guarded(ctx, r, pv, py, mis):
     ip, ix = torch.from_numpy(indptr).cuda(), torch.from_numpy(indices).cuda()
     ctx.check(ctx.lib.rt_csr_spmm(ctx.handle, P(ip), P(ix), P(dd), N, P(Vd), r + pv, r, P(Y.t), r + py), "rt_csr_spmm")
     A = sp.csr_matrix((data, indices, indptr), shape=(N, ncols))
-    _exact(_host(Y.t), A @ V)
+    got = _host(Y.t)
+    _exact(got, A @ V)
     _clean([Y], [(Vd, V), (dd, data[None, :])])
+    return got
+
+
+@pytest.mark.parametrize("r,pv,py,mis", CSR_SPMM_CASES)
+def test_csr_spmm_guarded(ctx, r, pv, py, mis):
+    _csr_spmm_case(ctx, r, pv, py, mis)
 
 
 # ---- rt_project_csr_batched --------------------------------------------------------------------------------------------
