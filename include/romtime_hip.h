@@ -190,6 +190,32 @@ int rt_transpose(rt_ctx* ctx, const double* src, int64_t rows, int64_t cols, int
 int rt_deim_greedy(rt_ctx* ctx, const double* Phi, int64_t N, int64_t m, int64_t ld, int layout,
                    int64_t* idx, double* PT_U, double* margin);
 
+/* One selection step of oversampled (M)DEIM, since version 450: more entries than modes, least squares in place of
+ * interpolation (gappy POD).  The rule is GappyPOD+E (Peherstorfer, Drmac, Gugercin, SIAM J. Sci. Comput. 42, 2020; the
+ * reference stops at m entries for m modes, deim.py:517-561).  With A = Phi[p, :] the rows picked so far, the host takes
+ * the thin SVD of A and hands over w (m DEVICE doubles), the right singular vector of the smallest singular value, and
+ * g = sigma_{m-1}^2 - sigma_m^2 (HOST double).  For every row i of Phi (N x m, ld and layout as for rt_deim_greedy)
+ *     rho_i = ||Phi[i, :]||^2,  c_i = Phi[i, :] . w,  a_i = g + rho_i,  q_i = 4 g c_i^2,
+ *     score_i = q_i / (a_i + sqrt(max(a_i^2 - q_i, 0)))   (0 where q_i = 0),
+ * half of which is a lower bound on the growth of sigma_min^2 when row i joins.  pick (one DEVICE int64) = the argmax over the rows whose
+ * byte in taken (N DEVICE bytes) is zero, the lowest index on ties, -1 when every row is taken; top2 (two DEVICE doubles)
+ * = the best score and the runner-up among those rows, -1 where there is none.  g = 0 gives all scores 0 and the lowest
+ * free index.  Enqueued on the ctx stream and not waited for.
+ *   - One pass over Phi (8 N m bytes): rho and c come from the row while it is in registers, nothing of size N is stored.
+ *     The sums of a row run in a fixed order that depends on the layout and m alone; workgroups of 512 rows reduce to
+ *     (top1, index, top2) in the order (score descending, index ascending) and a second launch of one workgroup merges the
+ *     partials (ctx leaf arena).  No floating-point atomics; the grid depends on N alone, so pick and top2 have the same
+ *     bits on any CU share ("cu_limit").
+ *   - A null pointer, N < 1, m < 2, a short ld, an unknown layout and a g that is negative or not finite return
+ *     RT_ERR_ARG; m > 1024 or N > 512 (2^31 - 1), beyond what rt_deim_greedy takes, RT_ERR_UNSUPPORTED; all before any launch.
+ *   - rt_last_launch_info: [0] workgroups, [1] lanes per row (1: column-major), [2] 512 rows per workgroup (512000). */
+int rt_deim_oversample_step(rt_ctx* ctx, const double* Phi, int64_t N, int64_t m, int64_t ld, int layout, const double* w,
+                            double g, const uint8_t* taken, int64_t* pick, double* top2);
+/* The argument checks and the launch plan of rt_deim_oversample_step - host logic only, no GPU and no pointer is followed:
+ * the same return code, and on RT_OK info3 (may be NULL) = {workgroups, rows per workgroup, lanes per row}. */
+int rt_deim_oversample_step_plan_info(const double* Phi, int64_t N, int64_t m, int64_t ld, int layout, const double* w, double g,
+                                      const uint8_t* taken, const int64_t* pick, const double* top2, int64_t* info3);
+
 /* ---- projections (src/romtime/utils.py:96-113,136-149; deim/mdeim.py:153-192) ----------- */
 
 /* Y (N x r row-major, ldy) = A V, A in CSR (N rows), V (n_colsA x r row-major, ldv).
@@ -234,6 +260,25 @@ int rt_dense_solve_batched(rt_ctx* ctx, double* K, double* rhs, int64_t r, int64
  * deim.py:477-493 applied once to every column of a projected collateral basis, when the interpolation matrix is folded
  * into the expansion of a hyper-reduced operator (romtime_amd/sweep.py). */
 int rt_dense_solve_multi(rt_ctx* ctx, const double* K, int64_t r, const double* B, double* X, int64_t nrhs, int* info);
+/* Least squares against ONE rows x cols matrix A, rows >= cols, for many right-hand sides, since version 450: what the
+ * theta solve and its folds become when oversampling makes PT_U rectangular (np.linalg.lstsq in the reference's terms).
+ * A row-major (device, untouched); B and X row-major (device, distinct, B untouched).
+ *   trans = 0: X (cols x nrhs) minimises ||A X - B||_2 column by column, B rows x nrhs (the theta fit);
+ *   trans = 1: X (rows x nrhs) is the minimum-norm solution of A^T X = B, B cols x nrhs: X = (A^+)^T B (the folds,
+ *              PT_U^T Z^T = basis_rom^T and PT_U^T Psi^T = basis_fom^T).
+ * Householder QR in LDS, factorised by every workgroup for itself, one thread per right-hand side (256 per workgroup);
+ * no normal equations.  A column's result depends neither on nrhs nor on its place.  *info (device int, may be NULL) =
+ * RT_WARN_SINGULAR on an exactly zero diagonal of R (a column that repeats an earlier one bit for bit gives one), else 0.
+ * For rows == cols the answers agree with rt_dense_solve_multi to rounding.  Limits: cols <= 128, rows <= 256 and
+ * rows x (cols | 1) <= 18432 (A beside its work space in the CU's 160 KiB of LDS; every rows x cols <= 16384 within the
+ * first two bounds fits); RT_ERR_UNSUPPORTED beyond.  Null pointers, B == X, sizes < 1, rows < cols and another trans
+ * return RT_ERR_ARG.  trans = 0 keeps a rows x nrhs work array in the ctx's leaf arena. */
+int rt_dense_lstsq_multi(rt_ctx* ctx, const double* A, int64_t rows, int64_t cols, int trans, const double* B, double* X,
+                         int64_t nrhs, int* info);
+/* The argument checks and the launch plan of rt_dense_lstsq_multi - host logic only, no GPU and no pointer is followed:
+ * the same return code, and on RT_OK info3 (may be NULL) = {workgroups, right-hand sides per workgroup, LDS bytes}. */
+int rt_dense_lstsq_multi_plan_info(const double* A, int64_t rows, int64_t cols, int trans, const double* B, const double* X,
+                                   int64_t nrhs, int64_t* info3);
 
 
 /* The same solve for a SEQUENCE of slowly changing matrices (the reduced systems of consecutive time steps differ by

@@ -63,12 +63,16 @@ SIGNATURES = {
     "rt_gemm_nn_axpby": (_int, [_p, _p, _i64, _int, _p, _i64, _i64, _i64, _i64, C.c_double, C.c_double, _p, _i64, _int]),
     "rt_transpose": (_int, [_p, _p, _i64, _i64, _i64, _p, _i64]),
     "rt_deim_greedy": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p, _p]),
+    "rt_deim_oversample_step": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, C.c_double, _p, _p, _p]),
+    "rt_deim_oversample_step_plan_info": (_int, [_p, _i64, _i64, _i64, _int, _p, C.c_double, _p, _p, _p, C.POINTER(_i64)]),
     "rt_csr_spmm": (_int, [_p, _p, _p, _p, _i64, _p, _i64, _i64, _p, _i64]),
     "rt_project_csr": (_int, [_p, _p, _p, _p, _i64, _p, _i64, _i64, _p]),
     "rt_project_csr_batched": (_int, [_p, _p, _p, _p, _i64, _int, _i64, _i64, _p, _i64, _i64, _p]),
     "rt_project_stage_info": (_int, [_p, _p, _p, _i64, C.POINTER(_i64), C.POINTER(_int)]),
     "rt_dense_solve_batched": (_int, [_p, _p, _p, _i64, _i64, _p]),
     "rt_dense_solve_multi": (_int, [_p, _p, _i64, _p, _p, _i64, _p]),
+    "rt_dense_lstsq_multi": (_int, [_p, _p, _i64, _i64, _int, _p, _p, _i64, _p]),
+    "rt_dense_lstsq_multi_plan_info": (_int, [_p, _i64, _i64, _int, _p, _p, _i64, C.POINTER(_i64)]),
     "rt_tracked_solve_batched": (_int, [_p, _p, _p, _p, _i64, _i64, _int, _p]),
     "rt_gmres_batched": (_int, [_p, _p, _p, _p, _i64, _i64, C.POINTER(GmresOpts), _p, _p]),
     "rt_ctx_set_reduced_solver": (_int, [_p, _int, C.POINTER(GmresOpts)]),

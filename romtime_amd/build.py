@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libromtime_hip.so")
-SOURCES = ["api.hip", "gemm_mfma.hip", "tallskinny.hip", "traj_error.hip", "traj_output.hip", "interp_error.hip", "traj_residual.hip", "rank_update.hip", "gram_mfma.hip", "deim.hip", "sparse.hip", "project_fused.hip", "solve.hip", "gmres.hip", "sweep.hip", "symeig.hip", "symeig_blocked.hip", "symjacobi.hip", "host_dense.cpp", "p1_assembly.hip", "p1_snapshots.hip", "p1_fom.hip", "pod_orth.hip"]
+SOURCES = ["api.hip", "gemm_mfma.hip", "tallskinny.hip", "traj_error.hip", "traj_output.hip", "interp_error.hip", "traj_residual.hip", "rank_update.hip", "gram_mfma.hip", "deim.hip", "deim_oversample.hip", "sparse.hip", "project_fused.hip", "solve.hip", "lstsq.hip", "gmres.hip", "sweep.hip", "symeig.hip", "symeig_blocked.hip", "symjacobi.hip", "host_dense.cpp", "p1_assembly.hip", "p1_snapshots.hip", "p1_fom.hip", "pod_orth.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # measurement builds only, e.g. ROMTIME_EXTRA_HIPFLAGS=-DROMTIME_PF_ABLATE (timing switches of csrc/project_fused.hip)
 FLAGS += os.environ.get("ROMTIME_EXTRA_HIPFLAGS", "").split()

@@ -187,7 +187,7 @@ int rt_profile_end(rt_ctx* ctx, bool also_gram) {
 
 extern "C" {
 
-int rt_version(void) { return 440; }  // 440: rt_p1_snapshot_sets (the (M)DEIM snapshot sets of the closed-form P1 operators over a product grid) and its _plan_info; 430: spare workgroup slots of the two-launch Gram take each tile's tail, rt_gram_spare_plan_info; 420: rt_trajectory_residuals (full-order residuals of lifted reduced trajectories), rt_trajectory_residuals_plan_info; 400: rt_sym_eig_blocked (block Rayleigh-Ritz on Gram matrices of 2049 .. 16384 snapshots), rt_sym_eig_blocked_plan_info, option pod_blocked, counters eig_blocked*; 390: rt_p1_fom_bdf_sweep (full-order BDF sweeps of the closed-form P1 models), rt_p1_fom_bdf_sweep_plan_info; 380: rt_interpolation_errors ((M)DEIM interpolation errors of whole snapshot sets), rt_interpolation_errors_plan_info; 370: rt_trajectory_integrals (mass and other integrals of whole trajectories), rt_trajectory_integrals_plan_info; 360: rt_sym_jacobi_eigh (device Jacobi for the two-pass POD); 350: rt_sym_eig_* and rt_pod_orth take n <= 2048 (wide tridiagonalisation), counter eig_wide_form; 340: rt_trajectory_errors; 330: rt_gmres_batched, rt_ctx_set_reduced_solver, counters sweep_gmres_*; 320: rt_gram_plan_info; 310: option gram_pace (paced / one-launch Gram); 300 (round 3): rt_dense_solve_multi, RT_P1_LOAD_P2; 210: rt_tracked_solve_batched, rt_pod_enqueue, options eig_xcd, counter gram_off_xcd
+int rt_version(void) { return 450; }  // 450: rt_deim_oversample_step (one GappyPOD+E selection step of oversampled (M)DEIM), rt_dense_lstsq_multi (Householder least squares against one rectangular matrix) and their _plan_info; 440: rt_p1_snapshot_sets (the (M)DEIM snapshot sets of the closed-form P1 operators over a product grid) and its _plan_info; 430: spare workgroup slots of the two-launch Gram take each tile's tail, rt_gram_spare_plan_info; 420: rt_trajectory_residuals (full-order residuals of lifted reduced trajectories), rt_trajectory_residuals_plan_info; 400: rt_sym_eig_blocked (block Rayleigh-Ritz on Gram matrices of 2049 .. 16384 snapshots), rt_sym_eig_blocked_plan_info, option pod_blocked, counters eig_blocked*; 390: rt_p1_fom_bdf_sweep (full-order BDF sweeps of the closed-form P1 models), rt_p1_fom_bdf_sweep_plan_info; 380: rt_interpolation_errors ((M)DEIM interpolation errors of whole snapshot sets), rt_interpolation_errors_plan_info; 370: rt_trajectory_integrals (mass and other integrals of whole trajectories), rt_trajectory_integrals_plan_info; 360: rt_sym_jacobi_eigh (device Jacobi for the two-pass POD); 350: rt_sym_eig_* and rt_pod_orth take n <= 2048 (wide tridiagonalisation), counter eig_wide_form; 340: rt_trajectory_errors; 330: rt_gmres_batched, rt_ctx_set_reduced_solver, counters sweep_gmres_*; 320: rt_gram_plan_info; 310: option gram_pace (paced / one-launch Gram); 300 (round 3): rt_dense_solve_multi, RT_P1_LOAD_P2; 210: rt_tracked_solve_batched, rt_pod_enqueue, options eig_xcd, counter gram_off_xcd
 
 int rt_ctx_create(rt_ctx** out, int device) {
   if (!out) return RT_ERR_ARG;

@@ -69,6 +69,13 @@ class DiscreteEmpiricalInterpolation(Reductor):
     # whole set of a parameter point in one launch (rt_p1_snapshot_sets), no callback; NotImplementedError where the
     # callback has no closed form.  The sets differ from the callbacks' by rounding, so the caller chooses.
     SNAPSHOTS_ON = "host"
+    # Entries per collateral mode.  1.0: the greedy's m entries for m modes and a square ``PT_U``, as the reference.  Above:
+    # the greedy's entries are extended to m_s = min(entries there are, ceil(OVERSAMPLING m)) by ``ops.deim_oversample``
+    # (GappyPOD+E), ``dofs`` has m_s entries, ``PT_U`` is m_s x m and every theta solve becomes a least-squares fit
+    # (``ops.dense_lstsq_multi``): 1 / sigma_min(PT_U), the error constant of the interpolation, can only shrink.  A basis
+    # of one mode keeps its one entry (the selection rule needs two singular values).
+    OVERSAMPLING = 1.0
+    LSTSQ_MAX_ROWS, LSTSQ_MAX_COLS, LSTSQ_MAX_WORDS = 256, 128, 18432      # rt_dense_lstsq_multi (include/romtime_hip.h)
 
     def __init__(self, assemble, grid=None, tree_walk_params=None, name=None) -> None:
         super().__init__(grid=grid)
@@ -84,6 +91,9 @@ class DiscreteEmpiricalInterpolation(Reductor):
         self.snapshots = None
         self.basis_pickle_name = self._basis_file_name()
         self._dev_cache = {}
+        self.greedy_margin = None
+        self.oversampling_margin = None
+        self.oversampling_sigma_min = None
 
     # deim.py:77-81; the reference dereferences ``name`` unconditionally and breaks on None
     def _basis_file_name(self):
@@ -114,7 +124,7 @@ class DiscreteEmpiricalInterpolation(Reductor):
             value = getattr(self, attr)
             if value is not None:
                 setattr(new, attr, deepcopy(value))
-        for attr in ("EVALUATE_ON", "SNAPSHOTS_ON", "closed_form"):      # instance overrides travel
+        for attr in ("EVALUATE_ON", "SNAPSHOTS_ON", "OVERSAMPLING", "closed_form"):      # instance overrides travel
             if attr in self.__dict__:
                 setattr(new, attr, self.__dict__[attr])
         return new
@@ -128,6 +138,20 @@ class DiscreteEmpiricalInterpolation(Reductor):
         if self.SNAPSHOTS_ON not in ("host", "device"):
             raise ValueError(f"SNAPSHOTS_ON must be 'host' or 'device', not {self.SNAPSHOTS_ON!r}")
         return self.SNAPSHOTS_ON == "device"
+
+    def _entries_target(self, m, available):
+        """m_s, the number of interpolation entries for m modes out of ``available`` (``OVERSAMPLING``)."""
+        f = self.OVERSAMPLING
+        if isinstance(f, bool) or not isinstance(f, (int, float, np.integer, np.floating)) or not np.isfinite(f) or f < 1.0:
+            raise ValueError(f"OVERSAMPLING must be a finite number >= 1, not {f!r}")
+        if m < 2:
+            return m
+        m_s = min(int(available), int(np.ceil(float(f) * m)))
+        if m_s > m and (m_s > self.LSTSQ_MAX_ROWS or m > self.LSTSQ_MAX_COLS or m_s * (m | 1) > self.LSTSQ_MAX_WORDS):
+            raise ValueError(f"{self}: {m_s} entries for {m} modes, the least-squares theta fit takes at most "
+                             f"{self.LSTSQ_MAX_ROWS} entries, {self.LSTSQ_MAX_COLS} modes and entries x (modes | 1) <= "
+                             f"{self.LSTSQ_MAX_WORDS}")
+        return m_s
 
     # ---- device residency of the (large) bases -----------------------------------------
     def _device(self, key, array):
@@ -177,11 +201,15 @@ class DiscreteEmpiricalInterpolation(Reductor):
         self.dofs = [(int(dof),) for dof in dofs]
 
     def build_interpolation_mesh(self):
-        """Greedy DEIM on the device (deim.py:517-561): returns ``(dofs, P)``."""
+        """Greedy DEIM on the device (deim.py:517-561), then the extra entries of ``OVERSAMPLING``: returns ``(dofs, P)``."""
         Vf = self.basis_fom
+        m_s = self._entries_target(Vf.shape[1], Vf.shape[0])               # a wrong factor or a limit: before any work
         idx, _, margin = ops.deim_greedy(self._device("basis_fom", Vf))
-        dofs = [int(i) for i in idx.cpu().numpy()]
         self.greedy_margin = margin.cpu().numpy()
+        self.oversampling_margin = self.oversampling_sigma_min = None
+        if m_s > Vf.shape[1]:
+            idx, _, self.oversampling_margin, self.oversampling_sigma_min = ops.deim_oversample(self._device("basis_fom", Vf), idx, m_s)
+        dofs = [int(i) for i in idx.cpu().numpy()]
         return dofs, InterpolationSelector(dofs, Vf.shape[0])
 
     def tree_walk(self, ts, normalize=True, num_mu=None, num_t=None, tol_mu=None, tol_t=None, num_snapshots=None,
@@ -270,7 +298,12 @@ class DiscreteEmpiricalInterpolation(Reductor):
 
     # ---- online --------------------------------------------------------------------------
     def compute_thetas(self, rhs):
-        """theta = solve(PT_U, rhs) (deim.py:477-493) by pivoted LU on the device."""
+        """theta = solve(PT_U, rhs) (deim.py:477-493) by pivoted LU on the device; with more entries than modes
+        (``OVERSAMPLING``) the least-squares fit min ||PT_U theta - rhs|| by Householder QR."""
+        if self.PT_U.shape[0] != self.PT_U.shape[1]:
+            rhs = ops.to_device(np.asarray(rhs, dtype=float).reshape(-1, 1))
+            theta, info = ops.dense_lstsq_multi(self._device("PT_U", self.PT_U), rhs)
+            return theta.reshape(-1).cpu().numpy()
         theta, info = ops.dense_solve(self._device("PT_U", self.PT_U), ops.to_device(np.asarray(rhs, dtype=float)))
         return theta.cpu().numpy()
 

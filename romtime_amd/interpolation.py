@@ -19,7 +19,7 @@ import torch
 from . import ops
 from .conventions import EmpiricalInterpolation, Stage
 
-MAX_M = 128                      # rt_interpolation_errors and rt_dense_solve_multi: the factors and a stage fit the LDS
+MAX_M = 128                      # interpolation ENTRIES (m_s with oversampling): rt_interpolation_errors and rt_dense_solve_multi
 MAX_COLUMNS = 4096               # snapshots per kernel call unless the caller says otherwise
 CLOSED_FORM_KINDS = ("mass", "stiffness", "convection", "nonlinear_lifting", "lifting", "trilinear", "forcing", "rhs")
 COLLECT_KINDS = ("trilinear", "forcing", "rhs")      # through ``collect.assemble`` (rt_p1_snapshot_sets)
@@ -29,7 +29,9 @@ def fold(reductor) -> torch.Tensor:
     """``Psi = basis_fom PT_U^-1`` (N_h x m) on the device, cached in the reductor against the identities of
     ``basis_fom`` and ``PT_U``: the interpolant of a snapshot f is then ``Psi f[idx]``.  Solved as
     ``PT_U^T Psi^T = basis_fom^T`` by the device's pivoted LU; a zero pivot raises what ``np.linalg.solve`` raises
-    (deim.py:491-492)."""
+    (deim.py:491-492).  With oversampled entries ``PT_U`` is m_s x m and ``Psi = basis_fom pinv(PT_U)`` is N_h x m_s, the
+    minimum-norm solution of the same equation by Householder QR (``ops.dense_lstsq_multi``): ``Psi f[idx]`` is the basis
+    times the least-squares theta.  ``MAX_M`` bounds the entries, m_s."""
     basis, PT_U = reductor.basis_fom, reductor.PT_U
     hit = reductor._dev_cache.get("interpolation_psi")
     if hit is not None and hit[0] is basis and hit[1] is PT_U:
@@ -37,9 +39,12 @@ def fold(reductor) -> torch.Tensor:
     m = int(np.shape(PT_U)[0])
     if m > MAX_M:
         raise ValueError(f"{reductor}: {m} interpolation entries, the device certification takes at most {MAX_M}")
-    K = ops.to_device(np.ascontiguousarray(np.asarray(PT_U, dtype=np.float64).T))
-    B = reductor._device("basis_fom", basis).T.contiguous()                       # m x N_h
-    Zt, info = ops.dense_solve_multi(K, B)
+    B = reductor._device("basis_fom", basis).T.contiguous()                       # modes x N_h
+    if np.shape(PT_U)[0] != np.shape(PT_U)[1]:        # oversampled entries: Psi = basis_fom pinv(PT_U), N_h x m_s
+        Zt, info = ops.dense_lstsq_multi(ops.to_device(np.ascontiguousarray(np.asarray(PT_U, dtype=np.float64))), B, trans=True)
+    else:
+        K = ops.to_device(np.ascontiguousarray(np.asarray(PT_U, dtype=np.float64).T))
+        Zt, info = ops.dense_solve_multi(K, B)
     if int(info.reshape(-1)[0].item()) != 0:
         raise np.linalg.LinAlgError("Singular matrix")
     Psi = Zt.T.contiguous()

@@ -33,6 +33,8 @@ class MatrixDiscreteEmpiricalInterpolationNonlinear(MatrixDiscreteEmpiricalInter
         Reductor.setup(self=truncated, rnd=self.random_state)
         truncated.rows, truncated.cols = self.rows, self.cols
         truncated.basis_fom = self.basis_fom[:, : N - n]
+        if "OVERSAMPLING" in self.__dict__:                                  # an instance override travels, as in ``copy``
+            truncated.OVERSAMPLING = self.__dict__["OVERSAMPLING"]
         truncated._finish_offline()
         truncated.mu_space = deepcopy(self.mu_space)
         truncated.report = deepcopy(self.report)

@@ -318,6 +318,92 @@ def deim_greedy(Phi: torch.Tensor, want_margin: bool = True):
     return idx, PT_U, margin
 
 
+def deim_oversample_step_plan(N: int, m: int, layout: int = ROW_MAJOR, ld: int = None):
+    """(workgroups, rows per workgroup, lanes per row) of ``deim_oversample_step`` - host logic only, no GPU
+    (rt_deim_oversample_step_plan_info); raises where the step would refuse the sizes."""
+    lib = _lib.load()
+    some = (C.c_double * 2)()   # the checks only see that the operands are there
+    sp = C.cast(some, _p)
+    ld = (int(N) if layout == COL_MAJOR else int(m)) if ld is None else int(ld)
+    info3 = (C.c_int64 * 3)()
+    rc = lib.rt_deim_oversample_step_plan_info(sp, int(N), int(m), ld, int(layout), sp, 1.0, sp, sp, sp, info3)
+    if rc != 0:
+        raise RomtimeHipError(f"rt_deim_oversample_step_plan_info failed ({rc}) for N = {N}, m = {m}, ld = {ld}")
+    return int(info3[0]), int(info3[1]), int(info3[2])
+
+
+def deim_oversample_step(Phi: torch.Tensor, w: torch.Tensor, g: float, taken: torch.Tensor, pick: torch.Tensor = None,
+                         top2: torch.Tensor = None):
+    """One GappyPOD+E selection step (rt_deim_oversample_step): ``(pick, top2)`` on the device and not waited for -
+    pick (int64[1]) the row of Phi (N x m, either memory order, any leading dimension) with the largest score among
+    the rows whose byte of ``taken`` (uint8[N]) is zero, -1 when there is none; top2 (float64[2]) the best score and the
+    runner-up.  ``w`` (float64[m]) and ``g`` come from the SVD of the rows picked so far (``deim_oversample``)."""
+    ctx = Context.current()
+    Phi, ld, lay = _layout(Phi)
+    N, m = Phi.shape
+    if (w.dtype != torch.float64 or not w.is_cuda or tuple(w.shape) != (m,) or not w.is_contiguous()
+            or taken.dtype != torch.uint8 or not taken.is_cuda or tuple(taken.shape) != (N,) or not taken.is_contiguous()):
+        raise RomtimeHipError("deim_oversample_step: w must be a contiguous float64[m] and taken a contiguous uint8[N] CUDA tensor")
+    pick = torch.empty(1, dtype=torch.int64, device=Phi.device) if pick is None else pick
+    top2 = torch.empty(2, dtype=torch.float64, device=Phi.device) if top2 is None else top2
+    ctx.check(ctx.lib.rt_deim_oversample_step(ctx.handle, _ptr(Phi), N, m, ld, lay, _ptr(w), float(g), _ptr(taken), _ptr(pick),
+                                              _ptr(top2)), "rt_deim_oversample_step")
+    return pick, top2
+
+
+def oversample_direction(rows: np.ndarray):
+    """(w, g, sigma) of the rows picked so far (len(p) x m, m >= 2, host): the right singular vector of the smallest
+    singular value, the gap sigma_{m-1}^2 - sigma_m^2 formed as a product so that it cannot come out negative, and the
+    singular values.  The one host step of ``deim_oversample``."""
+    _, s, Vt = np.linalg.svd(rows, full_matrices=False)
+    m = rows.shape[1]
+    g = float((s[m - 2] - s[m - 1]) * (s[m - 2] + s[m - 1]))
+    return np.ascontiguousarray(Vt[m - 1]), g, s
+
+
+def deim_oversample(Phi: torch.Tensor, idx, m_s: int):
+    """Oversampled (M)DEIM entries by GappyPOD+E (Peherstorfer, Drmac, Gugercin 2020): the m greedy indices ``idx`` of
+    the basis Phi (N x m, m >= 2) are extended to m_s <= N, every new one the row that is certified to raise
+    sigma_min(Phi[idx, :]) most.  Per added entry: the SVD of the rows gathered so far on the host (``oversample_direction``),
+    one pass over Phi on the device (``deim_oversample_step``), the pick and its row read back, the byte mask updated
+    on the device.  Returns ``(idx, PT_U, margin, sigma_min)``: idx (int64[m_s], device) whose first m entries are the
+    input, PT_U = Phi[idx, :] (m_s x m, device), margin ((top1 - top2) / top1 of the scores per added entry, host) and
+    sigma_min (host, m_s - m + 1 values: before the first addition and after each)."""
+    _need_gpu()
+    if Phi.dtype != torch.float64 or not Phi.is_cuda or Phi.dim() != 2:
+        raise RomtimeHipError("deim_oversample: Phi must be a 2-D float64 CUDA tensor")
+    N, m = Phi.shape
+    idx = idx if isinstance(idx, torch.Tensor) else to_device_index(idx, Phi.device)
+    idx = idx.to(device=Phi.device, dtype=torch.int64).reshape(-1)
+    m_s = int(m_s)
+    if idx.numel() != m or m < 2 or not m <= m_s <= N:
+        raise RomtimeHipError(f"deim_oversample: need m >= 2 indices for the m = {m} modes and m <= m_s <= N "
+                              f"(got {idx.numel()} indices, m_s = {m_s}, N = {N})")
+    rows = np.empty((m_s, m))
+    rows[:m] = Phi[idx, :].cpu().numpy()
+    out_idx = np.empty(m_s, dtype=np.int64)
+    out_idx[:m] = idx.cpu().numpy()
+    taken = torch.zeros(N, dtype=torch.uint8, device=Phi.device)
+    taken[idx] = 1
+    pick = torch.empty(1, dtype=torch.int64, device=Phi.device)
+    top2 = torch.empty(2, dtype=torch.float64, device=Phi.device)
+    margin, sigma_min = np.zeros(m_s - m), np.empty(m_s - m + 1)
+    for n in range(m, m_s):
+        w, g, s = oversample_direction(rows[:n])
+        sigma_min[n - m] = s[m - 1]
+        deim_oversample_step(Phi, to_device(w, Phi.device), g, taken, pick, top2)
+        p = int(pick.item())
+        if p < 0:
+            raise RomtimeHipError("deim_oversample: no free row left")
+        t1, t2 = top2.cpu().numpy()
+        margin[n - m] = (t1 - max(t2, 0.0)) / t1 if t1 > 0.0 else 0.0
+        rows[n] = Phi[p, :].cpu().numpy()
+        out_idx[n] = p
+        taken[p] = 1
+    sigma_min[m_s - m] = np.linalg.svd(rows, compute_uv=False)[m - 1]
+    return to_device_index(out_idx, Phi.device), to_device(rows, Phi.device), margin, sigma_min
+
+
 def csr_spmm(indptr, indices, data, V: torch.Tensor) -> torch.Tensor:
     ctx = Context.current()
     V = V.contiguous()
@@ -422,6 +508,40 @@ def dense_solve_multi(K: torch.Tensor, B: torch.Tensor):
     X = torch.empty_like(B)
     info = torch.zeros(1, dtype=torch.int32, device=K.device)
     ctx.check(ctx.lib.rt_dense_solve_multi(ctx.handle, _ptr(K), r, _ptr(B), _ptr(X), nrhs, _ptr(info)), "rt_dense_solve_multi")
+    return X, info
+
+
+def dense_lstsq_plan(rows: int, cols: int, nrhs: int = 1, trans: int = 0):
+    """(workgroups, right-hand sides per workgroup, LDS bytes) of ``dense_lstsq_multi`` - host logic only, no GPU
+    (rt_dense_lstsq_multi_plan_info); raises where the solve would refuse the sizes."""
+    lib = _lib.load()
+    some = (C.c_double * 4)()   # the checks only see that the operands are there and distinct
+    info3 = (C.c_int64 * 3)()
+    rc = lib.rt_dense_lstsq_multi_plan_info(C.cast(some, _p), int(rows), int(cols), int(trans), _p(C.addressof(some) + 8),
+                                            _p(C.addressof(some) + 16), int(nrhs), info3)
+    if rc != 0:
+        raise RomtimeHipError(f"rt_dense_lstsq_multi_plan_info failed ({rc}) for rows = {rows}, cols = {cols}, nrhs = {nrhs}")
+    return int(info3[0]), int(info3[1]), int(info3[2])
+
+
+def dense_lstsq_multi(A: torch.Tensor, B: torch.Tensor, trans: bool = False):
+    """Least squares against one rows x cols matrix A (rows >= cols; cols <= 128, rows <= 256) by Householder QR
+    (rt_dense_lstsq_multi).  ``trans`` False: X (cols x nrhs) minimises ||A X - B|| column by column, B rows x nrhs;
+    ``trans`` True: X (rows x nrhs) is the minimum-norm solution of A^T X = B, B cols x nrhs - X = pinv(A)^T B.
+    Returns (X, info); info is RT_WARN_SINGULAR where R has an exactly zero diagonal entry.  Inputs are not modified."""
+    ctx = Context.current()
+    A, B = A.contiguous(), B.contiguous()
+    if A.dim() != 2 or B.dim() != 2 or A.dtype != torch.float64 or B.dtype != torch.float64:
+        raise RomtimeHipError("dense_lstsq_multi: A and B must be 2-D float64 CUDA tensors")
+    rows, cols = A.shape
+    nrhs = B.shape[1]
+    if B.shape[0] != (cols if trans else rows):
+        raise RomtimeHipError(f"dense_lstsq_multi: B must have {cols if trans else rows} rows for A {tuple(A.shape)}, "
+                              f"trans = {bool(trans)}")
+    X = torch.empty((rows if trans else cols, nrhs), dtype=torch.float64, device=A.device)
+    info = torch.zeros(1, dtype=torch.int32, device=A.device)
+    ctx.check(ctx.lib.rt_dense_lstsq_multi(ctx.handle, _ptr(A), rows, cols, int(bool(trans)), _ptr(B), _ptr(X), nrhs, _ptr(info)),
+              "rt_dense_lstsq_multi")
     return X, info
 
 

@@ -81,9 +81,18 @@ def fold_term(PT_U, basis_rom) -> torch.Tensor:
     """The rows the local entries of a term multiply, ``Z^T = PT_U^-T basis_rom^T`` (m x r^2, or m x r for a vector
     term), on the device.  An identity ``PT_U`` (the terms of an affine model, ``online.hrom_terms_from_affine``) needs
     no solve; more than 128 entries are beyond the LDS-resident factorisation (include/romtime_hip.h) and go through
-    host LAPACK.  A zero pivot raises what ``np.linalg.solve`` raises (deim.py:491-492)."""
+    host LAPACK.  A zero pivot raises what ``np.linalg.solve`` raises (deim.py:491-492).  A rectangular ``PT_U`` (m_s x m,
+    oversampled entries) gives the m_s rows of ``Z^T = pinv(PT_U)^T basis_rom^T``, the minimum-norm solution of
+    ``PT_U^T Z^T = basis_rom^T`` by the device's Householder QR (``ops.dense_lstsq_multi``): ``Z f`` is then
+    ``basis_rom`` times the least-squares theta of the local entries f."""
     PT_U, basis_rom = np.asarray(PT_U, dtype=np.float64), np.asarray(basis_rom, dtype=np.float64)
     m = PT_U.shape[0]
+    if PT_U.shape[0] != PT_U.shape[1]:
+        Zt, info = ops.dense_lstsq_multi(ops.to_device(np.ascontiguousarray(PT_U)), ops.to_device(np.ascontiguousarray(basis_rom.T)),
+                                         trans=True)
+        if int(info.item()) != 0:
+            raise np.linalg.LinAlgError("Singular matrix")
+        return Zt
     if np.array_equal(PT_U, np.eye(m)):
         return ops.to_device(np.ascontiguousarray(basis_rom.T))
     if m > 128:
